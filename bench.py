@@ -20,7 +20,14 @@ DataParallel semantics).  value = all frames / max-over-ranks time.
 EWVIT_BENCH_REHEARSE=1 puts every rank on cuda:0 over gloo (eager; timings meaningless):
 the one-GPU rehearsal of the N-rank path.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--no-cpu-baseline] [--eager]
+A plain run sets up, warms up, times the K steps and prints the result line (metric, value,
+unit, higher_is_better, dtype, ms_per_step, the workload's config).  --full adds everything
+that takes runs of its own: the per-kernel event passes with their rooflines, the isolated DWT
+front-end timing and the CPU baseline (--no-cpu-baseline drops the last).  --dump-outputs DIR
+writes what the last timed step produced (dump_outputs: loss, parameters) as DIR/<name>.npy.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--full [--no-cpu-baseline]]
+                       [--dump-outputs DIR] [--eager]
 """
 import argparse
 import json
@@ -51,8 +58,14 @@ def parse():
                     help='BASELINE.json configs[k-1]: 2 = 224^2 64 frames dim 128 (3 = the same per GPU on '
                          'N GPUs), 4 = MWT branch at 384^2 32 frames dim 256, 5 = fp8 token GEMMs, 128 frames')
     ap.add_argument('--frames', type=int, default=None, help='frames per GPU per step (config default)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the per-kernel event passes (rooflines, kernel table, isolated DWT timing) '
+                         'and the CPU baseline; a plain run only times the steps')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-steps', type=int, default=4)
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write the last step\'s loss and the parameters it left as '
+                         'DIR/<name>.npy (float32)')
     ap.add_argument('--eager', action='store_true', help='issue every launch from Python (no HIP graph)')
     return ap.parse_args()
 
@@ -356,6 +369,137 @@ def workload(args, world, step):
             'launch': step.mode, 'baseline_config': 3 if world > 1 else args.config}
 
 
+DUMP_MAX_ELEMS = 7_000_000     # 28 MB of float32: the dump stays well under 64 MB
+
+
+def dump_outputs(step, out_dir):
+    """What the last timed step left its caller, as DIR/<name>.npy (float32): `loss`, the value
+    step() returned, and `params`, the trainable parameters after that step's Adam update,
+    flattened in model.parameters() order and concatenated.  A concatenation longer than
+    DUMP_MAX_ELEMS is cut to a fixed sample: the sorted first DUMP_MAX_ELEMS indices of a
+    permutation seeded with 0, the same for every run.  Inputs, initial weights and dropout
+    seeds are the same from run to run; the step's results are not bit-identical between runs
+    ("Known: results differ from run to run": after 25 steps the parameters differ by
+    about 1.2e-3 relative L2)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for p in step.model.parameters() if p.requires_grad]
+    n = sum(p.numel() for p in params)
+    flat = torch.cat([p.detach().float().flatten() for p in params])
+    if n > DUMP_MAX_ELEMS:
+        perm = torch.randperm(n, generator=torch.Generator().manual_seed(0))
+        flat = flat[perm[:DUMP_MAX_ELEMS].sort().values.to(flat.device)]
+    np.save(os.path.join(out_dir, 'loss.npy'), step.loss.detach().float().reshape(-1).cpu().numpy())
+    np.save(os.path.join(out_dir, 'params.npy'), flat.cpu().numpy())
+
+
+def kernel_passes(step, args):
+    """--full: the per-kernel event passes after the timed loop -> (table, shapes, iso_table, kt)."""
+    import ewvit
+    # per-kernel timing pass (HIP events around every ewvit launch, separate from the timed
+    # loop): the same iteration issued eagerly, so each launch can be bracketed
+    ewvit._lib.enable_timing(True)
+    kt = max(3, min(args.steps, 5))
+    for _ in range(kt):
+        step._eager()
+    torch.cuda.synchronize()
+    table = kernel_table(ewvit._lib.timing_records())
+    shapes = shape_table(ewvit._lib.timing_detail())
+    ewvit._lib.enable_timing(False)
+    for r in table.values():
+        r['per_step'] = r['launches'] / kt
+    # the same pass with the MWT on the main stream and uncapped grids: each kernel on the
+    # whole chip (the timed step runs the MWT's big launches on 128 of the 256 CUs, beside
+    # the backbone — network/dama.py _mwt_grid_cap — so their as-run durations are longer)
+    # (every rank runs it: the eager step issues the gradient all-reduces and the buffer
+    # broadcast, so a rank-0-only pass would wait on its peers forever)
+    iso_table = None
+    if args.config in (2, 3, 5):
+        saved = {k: os.environ.get(k) for k in ('EWVIT_BRANCH_STREAMS', 'EWVIT_MWT_GRID_CAP')}
+        os.environ['EWVIT_BRANCH_STREAMS'] = '0'
+        os.environ['EWVIT_MWT_GRID_CAP'] = '0'
+        try:
+            ewvit._lib.enable_timing(True)
+            for _ in range(kt):
+                step._eager()
+            torch.cuda.synchronize()
+            iso_table = kernel_table(ewvit._lib.timing_records())
+            ewvit._lib.enable_timing(False)
+        finally:
+            for k, v in saved.items():
+                if v is None:
+                    os.environ.pop(k, None)
+                else:
+                    os.environ[k] = v
+        for r in iso_table.values():
+            r['per_step'] = r['launches'] / kt
+    return table, shapes, iso_table, kt
+
+
+def full_report(res, step, args, table, shapes, iso_table, kt):
+    """--full: the rooflines, the kernel table, the isolated DWT timing and the CPU baseline of the line."""
+    dom = max(table.items(), key=lambda kv: kv[1]['total_ms']) if table else None
+    if table:
+        res['mfma_util'] = mfma_util(table, res['ms_per_step'])
+    opt = getattr(step, 'opt', None)
+    aps = opt.launches_per_step() if hasattr(opt, 'launches_per_step') else None
+    res['roofline'] = roofline_for(*dom, config=args.config, adam_per_step=aps) if dom else None
+    if res['roofline'] is not None:
+        cap = _mwt_cap()
+        res['roofline']['timing'] = ('HIP events around every launch of an eager pass of the step as it runs '
+                                     f'(MWT on its own stream, its big grids capped at {cap} workgroups)')
+    if iso_table and dom and dom[0] in iso_table:
+        iso = roofline_for(dom[0], iso_table[dom[0]], config=args.config, adam_per_step=aps)
+        iso['timing'] = 'same pass with one stream and uncapped grids (each kernel on the whole chip)'
+        res['roofline_isolated'] = iso
+    if shapes:
+        # the hottest single launch configuration (entry point + shape arguments)
+        h = dict(shapes[0])
+        h['per_step'] = h['launches'] / kt
+        hot = roofline_for(h['entry'], h, args.config, aps)
+        hot['traffic'] = None      # the PMC passes are summarised per kernel symbol, not per shape
+        hot['args'] = h['args']
+        res['roofline_hot'] = hot
+        res['top_launch_configs'] = [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}
+                                     for r in shapes[:12]]
+    # MFMA utilisation of the token path's GEMMs (ViT attention / MLP projections,
+    # patch_to_embedding, classifier: north_star's attention/MLP figure); at config 5 the
+    # attention / MLP projections are the fp8 entry point, priced against the fp8 peak
+    tok = 'ewvit_gemm_mx8' if (args.config == 5 and 'ewvit_gemm_mx8' in table) else 'ewvit_gemm'
+    if tok in table:
+        tg = roofline_for(tok, table[tok], args.config, aps)
+        tg['timing'] = res['roofline']['timing'] if res.get('roofline') else None
+        tg['launches_per_step'] = table[tok]['per_step']
+        res['token_gemm_roofline'] = tg
+    res['kernels'] = {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items()}
+                      for k, v in sorted(table.items(), key=lambda kv: -kv[1]['total_ms'])}
+    fe = next((e for e in ('ewvit_dwt_hf_upsample_fused', 'ewvit_dwt_haar_fwd') if e in table), None)
+    if fe is not None:
+        # the MWT front end: the fused DWT -> HF upsample launch (or the DWT of the two-launch
+        # path).  The per-launch events of the eager pass add ~10 us around a ~20 us kernel:
+        # the achieved rate is taken from back-to-back launches on the same frames replayed
+        # from one HIP graph (tools/dwt_bench.py; matches rocprofv3's kernel duration)
+        dr = roofline_for(fe, table[fe], args.config, aps)
+        sys.path.insert(0, os.path.join(REPO, 'tools'))
+        import dwt_bench
+        iso = dwt_bench.measure(n=args.frames, hw=384 if args.config == 4 else 224, levels=3)
+        k = 'fused' if fe == 'ewvit_dwt_hf_upsample_fused' else 'dwt'
+        dr['event_avg_us'] = dr['avg_us']
+        dr['avg_us'] = round(iso[k + '_us'], 3)
+        dr['work_per_launch'] = iso[k + '_bytes']
+        dr['achieved'] = round(iso[k + '_bytes'] / iso[k + '_us'] / 1e3, 2)
+        dr['frac'] = round(dr['achieved'] / HBM_PEAK_GBS, 5)
+        dr['timing'] = 'HIP graph of 50 back-to-back launches, events around the replay'
+        dr['channels'] = iso['channels']      # hf_conv input channels written (9: the real bands)
+        # the two-launch path it replaces, same frames: DWT (bands to HBM) + upsample
+        dr['two_launch'] = {n: {'avg_us': round(iso[n + '_us'], 3), 'work_per_launch': iso[n + '_bytes'],
+                                'achieved': round(iso[n + '_bytes'] / iso[n + '_us'] / 1e3, 2),
+                                'frac': round(iso[n + '_bytes'] / iso[n + '_us'] / 1e3 / HBM_PEAK_GBS, 5)}
+                            for n in ('dwt', 'up')}
+        res['dwt_roofline'] = dr
+    res['cpu_baseline'] = None if args.no_cpu_baseline else cpu_baseline(args.cpu_steps, args.config)
+
+
 def _free_port():
     s = socket.socket()
     s.bind(('127.0.0.1', 0))
@@ -412,43 +556,10 @@ def main():
     torch.cuda.synchronize()
     elapsed = edist.max_over_ranks(time.perf_counter() - t0, dev)
 
-    # per-kernel timing pass (HIP events around every ewvit launch, separate from the timed
-    # loop): the same iteration issued eagerly, so each launch can be bracketed
-    ewvit._lib.enable_timing(True)
-    kt = max(3, min(args.steps, 5))
-    for _ in range(kt):
-        step._eager()
-    torch.cuda.synchronize()
-    table = kernel_table(ewvit._lib.timing_records())
-    shapes = shape_table(ewvit._lib.timing_detail())
-    ewvit._lib.enable_timing(False)
-    for r in table.values():
-        r['per_step'] = r['launches'] / kt
-    # the same pass with the MWT on the main stream and uncapped grids: each kernel on the
-    # whole chip (the timed step runs the MWT's big launches on 128 of the 256 CUs, beside
-    # the backbone — network/dama.py _mwt_grid_cap — so their as-run durations are longer)
-    # (every rank runs it: the eager step issues the gradient all-reduces and the buffer
-    # broadcast, so a rank-0-only pass would wait on its peers forever)
-    iso_table = None
-    if args.config in (2, 3, 5):
-        saved = {k: os.environ.get(k) for k in ('EWVIT_BRANCH_STREAMS', 'EWVIT_MWT_GRID_CAP')}
-        os.environ['EWVIT_BRANCH_STREAMS'] = '0'
-        os.environ['EWVIT_MWT_GRID_CAP'] = '0'
-        try:
-            ewvit._lib.enable_timing(True)
-            for _ in range(kt):
-                step._eager()
-            torch.cuda.synchronize()
-            iso_table = kernel_table(ewvit._lib.timing_records())
-            ewvit._lib.enable_timing(False)
-        finally:
-            for k, v in saved.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
-        for r in iso_table.values():
-            r['per_step'] = r['launches'] / kt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step, args.dump_outputs)        # before --full's event passes run further steps
+    if args.full:
+        table, shapes, iso_table, kt = kernel_passes(step, args)
 
     if rank == 0:
         frames = args.frames * world * args.steps
@@ -462,67 +573,9 @@ def main():
                'dtype': 'fp8e4m3+bf16' if _gemm(args.config) == 'fp8' else 'bf16',
                'data': 'synthetic N(0,1) frames, random-init weights (no datasets/checkpoints offline)',
                'config': workload(args, world, step)}
-        dom = max(table.items(), key=lambda kv: kv[1]['total_ms']) if table else None
-        if table:
-            res['mfma_util'] = mfma_util(table, res['ms_per_step'])
-        opt = getattr(step, 'opt', None)
-        aps = opt.launches_per_step() if hasattr(opt, 'launches_per_step') else None
-        res['roofline'] = roofline_for(*dom, config=args.config, adam_per_step=aps) if dom else None
-        if res['roofline'] is not None:
-            cap = _mwt_cap()
-            res['roofline']['timing'] = ('HIP events around every launch of an eager pass of the step as it runs '
-                                         f'(MWT on its own stream, its big grids capped at {cap} workgroups)')
-        if iso_table and dom and dom[0] in iso_table:
-            iso = roofline_for(dom[0], iso_table[dom[0]], config=args.config, adam_per_step=aps)
-            iso['timing'] = 'same pass with one stream and uncapped grids (each kernel on the whole chip)'
-            res['roofline_isolated'] = iso
-        if shapes:
-            # the hottest single launch configuration (entry point + shape arguments)
-            h = dict(shapes[0])
-            h['per_step'] = h['launches'] / kt
-            hot = roofline_for(h['entry'], h, args.config, aps)
-            hot['traffic'] = None      # the PMC passes are summarised per kernel symbol, not per shape
-            hot['args'] = h['args']
-            res['roofline_hot'] = hot
-            res['top_launch_configs'] = [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()}
-                                         for r in shapes[:12]]
-        # MFMA utilisation of the token path's GEMMs (ViT attention / MLP projections,
-        # patch_to_embedding, classifier: north_star's attention/MLP figure); at config 5 the
-        # attention / MLP projections are the fp8 entry point, priced against the fp8 peak
-        tok = 'ewvit_gemm_mx8' if (args.config == 5 and 'ewvit_gemm_mx8' in table) else 'ewvit_gemm'
-        if tok in table:
-            tg = roofline_for(tok, table[tok], args.config, aps)
-            tg['timing'] = res['roofline']['timing'] if res.get('roofline') else None
-            tg['launches_per_step'] = table[tok]['per_step']
-            res['token_gemm_roofline'] = tg
-        res['kernels'] = {k: {kk: (round(vv, 4) if isinstance(vv, float) else vv) for kk, vv in v.items()}
-                          for k, v in sorted(table.items(), key=lambda kv: -kv[1]['total_ms'])}
-        fe = next((e for e in ('ewvit_dwt_hf_upsample_fused', 'ewvit_dwt_haar_fwd') if e in table), None)
-        if fe is not None:
-            # the MWT front end: the fused DWT -> HF upsample launch (or the DWT of the two-launch
-            # path).  The per-launch events of the eager pass add ~10 us around a ~20 us kernel:
-            # the achieved rate is taken from back-to-back launches on the same frames replayed
-            # from one HIP graph (tools/dwt_bench.py; matches rocprofv3's kernel duration)
-            dr = roofline_for(fe, table[fe], args.config, aps)
-            sys.path.insert(0, os.path.join(REPO, 'tools'))
-            import dwt_bench
-            iso = dwt_bench.measure(n=args.frames, hw=384 if args.config == 4 else 224, levels=3)
-            k = 'fused' if fe == 'ewvit_dwt_hf_upsample_fused' else 'dwt'
-            dr['event_avg_us'] = dr['avg_us']
-            dr['avg_us'] = round(iso[k + '_us'], 3)
-            dr['work_per_launch'] = iso[k + '_bytes']
-            dr['achieved'] = round(iso[k + '_bytes'] / iso[k + '_us'] / 1e3, 2)
-            dr['frac'] = round(dr['achieved'] / HBM_PEAK_GBS, 5)
-            dr['timing'] = 'HIP graph of 50 back-to-back launches, events around the replay'
-            dr['channels'] = iso['channels']      # hf_conv input channels written (9: the real bands)
-            # the two-launch path it replaces, same frames: DWT (bands to HBM) + upsample
-            dr['two_launch'] = {n: {'avg_us': round(iso[n + '_us'], 3), 'work_per_launch': iso[n + '_bytes'],
-                                    'achieved': round(iso[n + '_bytes'] / iso[n + '_us'] / 1e3, 2),
-                                    'frac': round(iso[n + '_bytes'] / iso[n + '_us'] / 1e3 / HBM_PEAK_GBS, 5)}
-                                for n in ('dwt', 'up')}
-            res['dwt_roofline'] = dr
         res['allreduce'] = step.describe() if hasattr(step, 'describe') else None
-        res['cpu_baseline'] = None if args.no_cpu_baseline else cpu_baseline(args.cpu_steps, args.config)
+        if args.full:
+            full_report(res, step, args, table, shapes, iso_table, kt)
         print(json.dumps(res), flush=True)
     if hasattr(step, 'close'):
         step.close()                 # graphs holding RCCL collectives released before the communicator

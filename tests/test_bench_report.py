@@ -83,6 +83,129 @@ def test_dominant_dgrad_traffic_ratio_matches_hand_count():
     assert 0.95 <= r['traffic_ratio'] <= 1.2, r['traffic_ratio']
 
 
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 2)
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--no-cpu-baseline', '--dump-outputs', 'd'])
+    a = bench.parse()
+    assert a.full and a.no_cpu_baseline and a.dump_outputs == 'd'
+
+
+def _run_main(monkeypatch, capsys, argv):
+    """bench.main() on the host with a stub step in place of the GPU one: -> (the result line,
+    the stub's call count, the --full functions that ran)."""
+    import json
+    import types
+    import torch
+    import bench
+    import ewvit
+    from ewvit import dist as edist
+    model = torch.nn.Linear(3, 2)
+    calls, ran = [], []
+
+    class Step:
+        mode, loss = 'graph', torch.tensor(0.25)
+
+        def __init__(self):
+            self.model = model
+
+        def __call__(self):
+            calls.append(1)
+            return self.loss
+
+        def _eager(self):
+            raise AssertionError('a plain run issued an eager pass')
+
+        def describe(self):
+            return {'launch': 'hip-graph', 'world': 1}
+
+        def close(self):
+            pass
+    for name in ('set_device', 'synchronize'):
+        monkeypatch.setattr(torch.cuda, name, lambda *a, **k: None)
+    monkeypatch.setattr(edist, 'rccl_env', lambda: None)
+    monkeypatch.setattr(edist, 'env_ranks', lambda: (0, 1, 0))
+    monkeypatch.setattr(edist, 'init_from_env', lambda *a, **k: None)
+    monkeypatch.setattr(edist, 'barrier', lambda: None)
+    monkeypatch.setattr(edist, 'max_over_ranks', lambda t, dev: t)
+    monkeypatch.setattr(ewvit, 'load_library', lambda: None)
+    monkeypatch.setattr(bench, 'build_step', lambda *a, **k: Step())
+
+    def passes(step, args):
+        ran.append('kernel_passes')
+        return {}, [], None, 3
+
+    def report(res, *a):
+        ran.append('full_report')
+        res['kernels'], res['roofline'], res['cpu_baseline'] = {}, None, None
+    monkeypatch.setattr(bench, 'kernel_passes', passes)
+    monkeypatch.setattr(bench, 'full_report', report)
+    monkeypatch.setattr(sys, 'argv', ['bench.py'] + argv)
+    bench.main()
+    line = capsys.readouterr().out.strip().splitlines()
+    assert len(line) == 1                                # one JSON result line
+    return json.loads(line[0]), len(calls), ran
+
+
+def test_plain_run_times_the_steps_and_nothing_else(monkeypatch, capsys, tmp_path):
+    """A plain run calls the step warmup + steps times, runs neither the event passes nor the
+    report behind --full, and its line holds the headline fields without the --full ones."""
+    res, n, ran = _run_main(monkeypatch, capsys, ['--gpus', '1', '--steps', '7', '--warmup', '2',
+                                                  '--dump-outputs', str(tmp_path / 'd')])
+    assert n == 9 and ran == []
+    for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert k in res, k
+    assert res['steps'] == 7 and res['warmup'] == 2 and res['unit'] == 'frames/s' and res['higher_is_better'] is True
+    assert isinstance(res['ms_per_step'], float) and res['ms_per_step'] >= 0 and res['value'] > 0
+    for k in ('kernels', 'roofline', 'roofline_isolated', 'roofline_hot', 'top_launch_configs', 'mfma_util',
+              'token_gemm_roofline', 'dwt_roofline', 'cpu_baseline'):
+        assert k not in res, k
+    assert sorted(f.name for f in (tmp_path / 'd').iterdir()) == ['loss.npy', 'params.npy']
+
+
+def test_full_run_adds_the_passes_and_the_report(monkeypatch, capsys):
+    res, n, ran = _run_main(monkeypatch, capsys, ['--gpus', '1', '--steps', '3', '--warmup', '1', '--full'])
+    assert n == 4 and ran == ['kernel_passes', 'full_report']
+    assert 'kernels' in res and 'cpu_baseline' in res and 'ms_per_step' in res
+
+
+def test_dump_outputs_writes_loss_and_params(tmp_path, monkeypatch):
+    """float32 .npy files, the trainable parameters in model.parameters() order; a long
+    concatenation is cut to the same seeded sample of indices, identical from call to call."""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(5, 7), torch.nn.Linear(7, 3)).double()
+    model[1].bias.requires_grad_(False)
+    loss = model(torch.randn(4, 5).double()).square().mean().detach()
+    step = types.SimpleNamespace(model=model, loss=loss)
+    flat = torch.cat([p.detach().float().flatten() for p in model.parameters() if p.requires_grad]).numpy()
+    assert flat.size == 5 * 7 + 7 + 7 * 3
+
+    bench.dump_outputs(step, str(tmp_path / 'a'))
+    assert sorted(f.name for f in (tmp_path / 'a').iterdir()) == ['loss.npy', 'params.npy']
+    got = {n: np.load(tmp_path / 'a' / f'{n}.npy') for n in ('loss', 'params')}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got['loss'].shape == (1,) and got['loss'][0] == np.float32(loss.item())
+    assert np.array_equal(got['params'], flat)
+
+    monkeypatch.setattr(bench, 'DUMP_MAX_ELEMS', 10)
+    bench.dump_outputs(step, str(tmp_path / 'b'))
+    bench.dump_outputs(step, str(tmp_path / 'c'))
+    idx = torch.randperm(flat.size, generator=torch.Generator().manual_seed(0))[:10].sort().values.numpy()
+    b, c = np.load(tmp_path / 'b' / 'params.npy'), np.load(tmp_path / 'c' / 'params.npy')
+    assert b.shape == (10,) and np.array_equal(b, c) and np.array_equal(b, flat[idx])
+
+
+def test_dump_budget_is_under_64_mb():
+    import bench
+    assert 4 * (bench.DUMP_MAX_ELEMS + 1) <= 64 * 10 ** 6
+
+
 def test_mfma_util_counts_mfma_entries_only():
     import bench
     table = {'ewvit_conv2d_fwd': dict(_row(0, 0), flops_per_launch=1e12, per_step=2.0),

@@ -20,13 +20,13 @@ if [[ $STEPS == all || $STEPS == *smoke* ]]; then
 fi
 if [[ $STEPS == all || $STEPS == *bench* ]]; then
   BL=${BENCH_LOG:-bench.log}
-  timeout -k 10 600 python "$R/bench.py" ${BENCH_ARGS:-} > "$O/$BL" 2>&1
+  timeout -k 10 600 python "$R/bench.py" --full ${BENCH_ARGS:-} > "$O/$BL" 2>&1
   rc=$?; echo "bench rc=$rc"; tail -1 "$O/$BL" | cut -c1-400; [ $rc -eq 0 ] || exit $rc
 fi
 if [[ $STEPS == all || $STEPS == *prof* ]]; then
   cd /tmp && export TMPDIR=/tmp
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/prof" -o run --output-format csv -- \
-      python3 "$R/bench.py" --steps 5 --warmup 2 --no-cpu-baseline > "$O/prof.log" 2>&1
+      python3 "$R/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline > "$O/prof.log" 2>&1
   rc=$?; echo "rocprof rc=$rc"; [ $rc -eq 0 ] || exit $rc
 fi
 echo done

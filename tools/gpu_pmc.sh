@@ -13,7 +13,7 @@ HB=$!
 trap 'kill $HB 2>/dev/null' EXIT
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 600 rocprofv3 --pmc $C --kernel-trace --output-format csv -d "$O/pmc_$C" -o run -- \
-      python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > "$O/pmc_$C.log" 2>&1
+      python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > "$O/pmc_$C.log" 2>&1
   rc=$?; echo "pmc $C rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done
 F=$(ls "$O"/pmc_FETCH_SIZE/*counter_collection.csv | head -1)

@@ -10,7 +10,7 @@ if [ -n "${TESTS:-}" ]; then
   rc=$?; echo "pytest rc=$rc"; tail -4 "$O/quick_tests.log"; [ $rc -eq 0 ] || exit $rc
 fi
 if [ "${NOBENCH:-0}" != 1 ]; then
-  timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > "$O/bench_quick.log" 2>&1
+  timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > "$O/bench_quick.log" 2>&1
   rc=$?; echo "bench rc=$rc"; tail -1 "$O/bench_quick.log" | cut -c1-300; [ $rc -eq 0 ] || exit $rc
 fi
 echo done
