@@ -25,6 +25,7 @@
 // batch variance for running_var and the biased one for normalisation.
 #include "common.h"
 
+#include <array>
 #include <cstdlib>
 
 namespace ewvit {
@@ -157,14 +158,13 @@ static BnGeo bn_geo(int64_t C) {
 static int bn_cap() { return g_grid_cap > 0 ? g_grid_cap : 0; }
 
 // (A/B) EWVIT_BN_GEO="reduction blocks:reduction rows per thread:elementwise blocks:elementwise
-// rows per thread" overrides the four constants below (read once)
+// rows per thread" overrides the four constants below (read once; launches come from several threads)
 static int bn_knob(int which, int dflt) {
-  static int v[4] = {-1, -1, -1, -1};
-  static bool init = false;
-  if (!init) {
-    init = true;
-    if (const char *e = getenv("EWVIT_BN_GEO")) sscanf(e, "%d:%d:%d:%d", &v[0], &v[1], &v[2], &v[3]);
-  }
+  static const std::array<int, 4> v = [] {
+    std::array<int, 4> r = {-1, -1, -1, -1};
+    if (const char *e = getenv("EWVIT_BN_GEO")) sscanf(e, "%d:%d:%d:%d", &r[0], &r[1], &r[2], &r[3]);
+    return r;
+  }();
   return v[which] > 0 ? v[which] : dflt;
 }
 

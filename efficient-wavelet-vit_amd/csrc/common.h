@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <cstdio>
 #include <cstdarg>
+#include <utility>
 
 #include "../../include/ewvit.h"
 
@@ -40,6 +41,16 @@ inline int launch_status(const char *what) {
 }
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
+
+// key of host state kept per stream: (device, stream) — PyTorch's default stream is handle 0 on
+// every device.  The device is the calling thread's current one (every valid launch has its
+// stream's device current); hipGetDevice is legal during stream capture
+typedef std::pair<int, uintptr_t> StreamKey;
+inline StreamKey stream_key(hipStream_t s) {
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  return {dev, reinterpret_cast<uintptr_t>(s)};
+}
 
 // ---------------------------------------------------------------- bf16
 typedef unsigned short bf16_t;

@@ -1,5 +1,10 @@
-// Shared declarations of the conv kernels (conv.hip: the generic implicit-GEMM family;
-// convwin.hip: the windowed 3x3 stride-1 kernels of the MWT's big maps).
+// Shared declarations of the conv kernels.  One translation unit per kernel family, each owning
+// its kernels and their launchers and exposing plain host functions here:
+//   conv_reg.hip    register-staged fwd / dgrad, the small-channel 3x3
+//   conv_glds.hip   LDS-DMA fwd / dgrad, its split-K epilogue and scratch
+//   conv_wgrad.hip  the weight gradients, their reduce and entry points
+//   convwin.hip     the windowed 3x3 stride-1 kernels of the MWT's big maps
+//   conv.hip        weight packs, argument validation, the fwd / dgrad entry points
 #pragma once
 #include "common.h"
 
@@ -62,7 +67,7 @@ struct FwdArgs {
   // coefficients (ewvit_bn_coef) — instead of x; channel group g = c / sgc, zero padding after
   // the transform
   const float *xf = nullptr;
-  // split K (LDS-DMA 1x1 fwd / dgrad over few tiles, conv.hip launch_glds): work item i is
+  // split K (LDS-DMA 1x1 fwd / dgrad over few tiles, conv_glds.hip launch_glds): work item i is
   // (tile i / ksplit, K-range i % ksplit of nk / ksplit K-tiles), which stores its fp32 partial
   // tile at kpart[split][M][Ncol]; conv_splitk_epi_kernel sums the splits and runs the epilogue
   int ksplit = 1;
@@ -172,6 +177,67 @@ __device__ __forceinline__ int swz_off(int r, int ch) {
   return 256 * r + 16 * (ch ^ (((r & 3) << 2) | ((r >> 2) & 3)));
 }
 
+// ---------------------------------------------------------------- host
+inline ConvGeom mkg(int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int ks, int stride) {
+  ConvGeom g;
+  g.N = (int)N; g.H = (int)H; g.W = (int)W; g.Cin = (int)Cin; g.Cout = (int)Cout; g.stride = stride;
+  g.ks = ks; g.pad = ks / 2;
+  g.Ho = (int)((H - 1) / stride + 1);
+  g.Wo = (int)((W - 1) / stride + 1);
+  return g;
+}
+// bytes a grouped channels-last bf16 tensor spans (gs == 0: plain NHWC)
+inline int64_t grouped_bytes(int64_t pixels, int64_t C, int64_t gc, int64_t gs) {
+  return 2 * (gs ? (C / gc - 1) * gs + pixels * gc : pixels * C);
+}
+// the forward GEMM of g: rows = y pixels, columns = Cout, per-tap K = Cin, x grouped (gc, gs) ...
+inline FwdArgs fwd_args(const ConvGeom &g, int64_t x_gc, int64_t x_gs) {
+  FwdArgs a;
+  a.g = g;
+  a.M = (int64_t)g.N * g.Ho * g.Wo; a.Ncol = g.Cout; a.KC = g.Cin;
+  a.srcH = g.H; a.srcW = g.W; a.outH = g.Ho; a.outW = g.Wo;
+  a.sgc = (int)x_gc; a.sgs = x_gs; a.ogc = g.Cout; a.ogs = 0;
+  return a;
+}
+// ... and the input-gradient GEMM, the transposed roles: rows = dx pixels, columns = Cin,
+// per-tap K = Cout, dx grouped (gc, gs).  Callers set only pointers and options.
+inline FwdArgs dgrad_args(const ConvGeom &g, int64_t dx_gc, int64_t dx_gs) {
+  FwdArgs a;
+  a.g = g;
+  a.M = (int64_t)g.N * g.H * g.W; a.Ncol = g.Cin; a.KC = g.Cout;
+  a.srcH = g.Ho; a.srcW = g.Wo; a.outH = g.H; a.outW = g.W;
+  a.sgc = g.Cout; a.sgs = 0; a.ogc = (int)dx_gc; a.ogs = dx_gs;
+  return a;
+}
+inline WgradArgs wgrad_args(const ConvGeom &g, int64_t x_gc, int64_t x_gs) {
+  WgradArgs a;
+  a.g = g;
+  a.M = (int64_t)g.N * g.Ho * g.Wo;
+  a.xgc = (int)x_gc; a.xgs = x_gs;
+  return a;
+}
+// argument validation (conv.hip); check_group normalises gc == 0 (plain NHWC) to (C, 0)
+int check_geom(const ConvGeom &g, const char *nm);
+int check_group(int64_t &gc, int64_t &gs, int64_t C, int64_t pixels, const char *nm, const char *which);
+// the problems of a conv reading relu(x * scale + shift) in the windowed kernels (conv.hip):
+// false when they do not take the shape
+bool xf_args(FwdArgs &a, WgradArgs &w, const ConvGeom &g, int64_t x_group_c, int64_t x_group_stride);
+
+// Kernel family: 1 (default) the LDS-DMA kernels wherever the shape allows them, the
+// register-staged kernels elsewhere; 0 the register-staged kernels everywhere — a test
+// switch (ewvit_conv2d_set_glds): they are the fallback of the shapes the LDS-DMA kernels
+// refuse, so the tests run every case through both.
+extern int g_glds;   // (conv_glds.hip)
+inline bool use_glds() { return g_glds != 0; }
+// the register-staged fwd / dgrad (conv_reg.hip): takes every shape; the small-channel 3x3:
+// true when it ran the shape
+void launch_fwd(const FwdArgs &a, bool dgrad, hipStream_t s);
+bool launch_small(const FwdArgs &a, bool dgrad, hipStream_t s);
+// the LDS-DMA fwd / dgrad (conv_glds.hip): true when it ran the shape (*bm_out: its row tile);
+// its tile for a shape; the stride-2 3x3 dgrad as one launch per output parity class
+bool launch_glds(const FwdArgs &a, int64_t src_bytes, bool dgrad, hipStream_t s, int *bm_out = nullptr);
+void glds_tile(const FwdArgs &a, bool dgrad, int &bm, int &bn);
+bool dgrad_by_parity(FwdArgs a, int64_t src_bytes, hipStream_t s);
 // the windowed 3x3 stride-1 fwd / dgrad (convwin.hip): true when it ran the shape
 bool launch_win(const FwdArgs &a, int64_t src_bytes, bool dgrad, hipStream_t s);
 bool win_ok(const FwdArgs &a, bool dgrad);

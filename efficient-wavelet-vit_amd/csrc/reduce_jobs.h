@@ -1,6 +1,6 @@
 // Deferred weight-gradient reductions.
 //
-// The backbone's split-K weight gradients (1x1 / LDS-DMA kernels, conv.hip) and the depthwise
+// The backbone's split-K weight gradients (1x1 / LDS-DMA kernels, conv_wgrad.hip) and the depthwise
 // backward (depthwise.hip) leave fp32 partial slabs that a small reduce kernel sums into dW:
 // ~110 launches of 5 us per backbone backward pass, each a kernel boundary on the critical
 // path.  A caller that knows nothing reads dW before the end of the backward pass (the
@@ -125,7 +125,8 @@ __device__ __forceinline__ void run_red_jobs(const RedJobs &r, int b, float *red
   }
 }
 
-// ---- host registry (conv.hip): per-stream FIFO of deferred jobs
+// ---- host registry (reduce_jobs.hip): FIFO of deferred jobs per (device, stream), the device
+// being the caller's current one (common.h StreamKey)
 bool reduce_take_defer();                         // consume this thread's "defer the next reduce" mark
 void reduce_defer(hipStream_t s, const RedJob &j);
 RedJobs reduce_take_jobs(hipStream_t s);          // up to 2 oldest jobs of stream s (nblk 0: none)

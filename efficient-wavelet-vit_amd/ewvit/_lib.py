@@ -209,9 +209,9 @@ def load():
         fn.argtypes = args
         fn.restype = res
     if os.environ.get('EWVIT_SMALL_TILES') == '0' and hasattr(lib, 'ewvit_conv2d_set_small_tiles'):
-        lib.ewvit_conv2d_set_small_tiles(0)          # A/B switch (conv.hip glds_tile)
+        lib.ewvit_conv2d_set_small_tiles(0)          # A/B switch (conv_glds.hip glds_tile)
     if os.environ.get('EWVIT_CONV_KSPLIT') and hasattr(lib, 'ewvit_conv2d_set_ksplit'):
-        lib.ewvit_conv2d_set_ksplit(int(os.environ['EWVIT_CONV_KSPLIT']))   # A/B (conv.hip split K)
+        lib.ewvit_conv2d_set_ksplit(int(os.environ['EWVIT_CONV_KSPLIT']))   # A/B (conv_glds.hip split K)
     if os.environ.get('EWVIT_LDS_PAD') == '0' and hasattr(lib, 'ewvit_conv2d_set_lds_pad'):
         lib.ewvit_conv2d_set_lds_pad(0)              # A/B switch (convwin.hip lds_pad)
     if os.environ.get('EWVIT_WGWIN_TS') in ('0', '2') and hasattr(lib, 'ewvit_conv2d_set_wgrad_tap_split'):
@@ -219,7 +219,7 @@ def load():
     if os.environ.get('EWVIT_WIN_NT', '').isdigit() and hasattr(lib, 'ewvit_conv2d_set_win_nt'):
         lib.ewvit_conv2d_set_win_nt(int(os.environ['EWVIT_WIN_NT']))   # A/B switch (convwin.hip g_win_nt)
     if os.environ.get('EWVIT_WGRAD_WIDE') in ('0', '2') and hasattr(lib, 'ewvit_conv2d_set_wgrad_wide'):
-        lib.ewvit_conv2d_set_wgrad_wide(int(os.environ['EWVIT_WGRAD_WIDE']))   # A/B (conv.hip wgrad_wide)
+        lib.ewvit_conv2d_set_wgrad_wide(int(os.environ['EWVIT_WGRAD_WIDE']))   # A/B (conv_wgrad.hip wgrad_wide)
     if os.environ.get('EWVIT_W1X1') and hasattr(lib, 'ewvit_conv2d_set_wgrad_1x1'):
         # A/B: the 1x1 weight gradient's split rule "workgroup target:min K-tiles per split[:ring]"
         v = [int(x) for x in os.environ['EWVIT_W1X1'].split(':')]

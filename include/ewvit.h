@@ -570,8 +570,10 @@ int ewvit_conv2d_bwd_weight(const void *x, const void *dy, float *dw, float *dbi
  * ewvit_reduce_flush(stream) launches whatever is still queued on `stream`.  Summation order
  * is the reduce kernel's: results are bit-identical to the immediate form.  The mark is
  * consumed by the next ewvit_conv2d_bwd_weight / ewvit_dwconv3x3_bwd_fused call whatever path
- * it takes.  ewvit_reduce_pending(stream) counts queued jobs (stream NULL: all streams).
- * Replaces the per-call reduce of torch's weight-gradient convs (reached through
+ * it takes.  ewvit_reduce_pending(stream) counts queued jobs (stream NULL: all streams of all
+ * devices).  A queue belongs to (device, stream) — the default stream is handle 0 on every
+ * device — the device being the caller's current one, which must be the stream's, as for any
+ * launch.  Replaces the per-call reduce of torch's weight-gradient convs (reached through
  * network/sfe.py:111-113, the EfficientNetV2-S backbone). */
 int ewvit_reduce_defer_next(int on);
 int ewvit_reduce_flush(void *stream);

@@ -1,5 +1,5 @@
 """BatchNorm statistics summed by the neighbouring kernels (csrc/depthwise.hip
-dw_row_bn_kernel, csrc/conv.hip dgrad epilogue, csrc/batchnorm.hip ewvit_bn_bwd_partials):
+dw_row_bn_kernel, csrc/conv_glds.hip dgrad epilogue, csrc/batchnorm.hip ewvit_bn_bwd_partials):
 the MBConv block's BatchNorms with no statistics / reduction pass of their own.
 
 Kernel level (through the C-ABI): the stored outputs are bit-identical to the plain kernels

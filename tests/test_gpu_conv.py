@@ -1,4 +1,4 @@
-"""Implicit-GEMM conv kernels (csrc/conv.hip, kernel 1x1 / 3x3) through the C-ABI,
+"""Implicit-GEMM conv kernels (csrc/conv*.hip, kernel 1x1 / 3x3) through the C-ABI,
 vs torch fp32 conv2d on the same bf16-rounded operands.
 
 Tolerance: outputs / input-grads are rounded to bf16 once (fp32 accumulation of

@@ -1,4 +1,4 @@
-"""Split K of the LDS-DMA 1x1 forward / input gradient (csrc/conv.hip launch_glds, FwdArgs::ksplit,
+"""Split K of the LDS-DMA 1x1 forward / input gradient (csrc/conv_glds.hip launch_glds, FwdArgs::ksplit,
 conv_splitk_epi_kernel) on the backbone's long-K 1x1 shapes (EfficientNetV2-S MBConv project
 forward / expand input gradient of stages 4-6 and the head conv, sfe.py:111-113) plus a ragged
 row count, through the C-ABI:
@@ -139,8 +139,41 @@ def test_ksplit_input_gradient_with_bn_sums(N, H, W, K, Nin):
         assert float(((pb - rb).abs() / mb.clamp_min(1e-12)).max()) < 1e-5
 
 
+def test_ksplit_second_stream():
+    """The split forward on a side stream (its own partials scratch: one per (device, stream);
+    the device half needs two GPUs and is not exercised here): the default stream's bits."""
+    L = _L()
+    lib = L.load()
+    N, H, W, K, Nout = SHAPES[-1]
+    g = torch.Generator().manual_seed(5)
+    x = bf(torch.randn(N, K, H, W, generator=g))
+    w = (torch.randn(Nout, K, generator=g) / K ** 0.5).to(DEV, torch.bfloat16).contiguous()
+    bias = (torch.randn(Nout, generator=g) * 0.1).to(DEV)
+    shift = (torch.randn(Nout, generator=g) * 0.05).to(DEV)
+    rows = int(lib.ewvit_conv2d_fwd_bn_rows(N, H, W, K, Nout, 1, 1))
+    nrc = (N * H * W + rows - 1) // rows
+    torch.cuda.synchronize()
+    outs = []
+    prev = lib.ewvit_conv2d_set_ksplit(KS_ON)
+    try:
+        for st in (torch.cuda.current_stream(), torch.cuda.Stream()):
+            with torch.cuda.stream(st):
+                y = torch.empty(N, Nout, H, W, device=DEV, dtype=torch.bfloat16).contiguous(memory_format=torch.channels_last)
+                part = torch.full((nrc, 2 * Nout), float('nan'), device=DEV)
+                so = torch.empty(Nout, device=DEV)
+                L.call('ewvit_conv2d_fwd_bn', L.ptr(x), L.ptr(w), L.ptr(bias), L.ptr(y), N, H, W, K, Nout, 1, 1, K, 0,
+                       L.ptr(shift), L.ptr(part), L.ptr(so), L.stream(y))
+            torch.cuda.synchronize()
+            outs.append((y, part))
+    finally:
+        lib.ewvit_conv2d_set_ksplit(KS_DEFAULT)        # the default limits back
+        lib.ewvit_conv2d_set_ksplit(prev)
+    assert not torch.isnan(outs[0][1]).any()
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+
+
 def test_ksplit_switch_restores():
-    """off by default (measured slower in the step, conv.hip g_ksplit)"""
+    """off by default (measured slower in the step, conv_glds.hip g_ksplit)"""
     L = _L()
     lib = L.load()
     assert lib.ewvit_conv2d_set_ksplit(1) == 0

@@ -94,6 +94,38 @@ def test_defer_mark_consumed_by_next_call():
     torch.testing.assert_close(dw, dw2, rtol=1e-5, atol=1e-4)
 
 
+def test_two_streams_isolated():
+    """Jobs are queued per stream: a deferred wgrad on side stream A stays queued through a
+    non-deferred wgrad and a flush on side stream B, and runs in A's flush; both dW equal the
+    immediate reduce.  (The queue's key is (device, stream); the device half needs two GPUs and
+    is not exercised here.)"""
+    lib = _lib().load()
+    g = torch.Generator(device=DEV).manual_seed(9)
+    shp_a, shp_b = (8, 28, 28, 64, 256), (4, 14, 14, 64, 128)
+    xa, xb = (torch.randn(*s[:4], device=DEV, generator=g).to(torch.bfloat16) for s in (shp_a, shp_b))
+    dya, dyb = (torch.randn(*s[:3], s[4], device=DEV, generator=g).to(torch.bfloat16) for s in (shp_a, shp_b))
+    ref_a, _ = _wgrad(xa, dya, 1, False, *shp_a)
+    ref_b, _ = _wgrad(xb, dyb, 1, False, *shp_b)
+    torch.cuda.synchronize()
+    assert _pending() == 0
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    ha, hb = ctypes.c_void_p(sa.cuda_stream), ctypes.c_void_p(sb.cuda_stream)
+
+    def pending(h):
+        return int(lib.ewvit_reduce_pending(h))
+    with torch.cuda.stream(sa):
+        dwa, wsa = _wgrad(xa, dya, 1, True, *shp_a)
+    with torch.cuda.stream(sb):
+        dwb, wsb = _wgrad(xb, dyb, 1, False, *shp_b)
+    assert pending(ha) == 1 and pending(hb) == 0
+    assert lib.ewvit_reduce_flush(hb) == 0
+    assert pending(ha) == 1
+    assert lib.ewvit_reduce_flush(ha) == 0
+    assert pending(ha) == 0 and _pending() == 0
+    torch.cuda.synchronize()                         # (wsa / wsb alive until here)
+    assert torch.equal(dwa, ref_a) and torch.equal(dwb, ref_b)
+
+
 class _NoOpt:
     def __init__(self, params):
         self.params = list(params)

@@ -1,4 +1,4 @@
-"""The 1x1 stride-1 weight-gradient kernel (csrc/conv.hip conv_wgrad_1x1_kernel) through the
+"""The 1x1 stride-1 weight-gradient kernel (csrc/conv_wgrad.hip conv_wgrad_1x1_kernel) through the
 C-ABI, on the backbone's 1x1 shapes (MBConv expand / project of stages 2-6 and the head conv of
 sfe.py:111-113's EfficientNetV2-S at 224^2, 64 frames) plus ragged tiles:
   * against torch fp32 of the same bf16 operands, dW = dy^T x (1e-5 of the largest entry);
@@ -45,7 +45,7 @@ def test_wgrad_1x1(N, Cin, H, W, Cout):
     # transposed view (s_ci = Cout) that cannot take the direct store
     dwt = torch.full((Cin, Cout, 1, 1), float('nan'), device=DEV).permute(1, 0, 2, 3)
     _wgrad(lib, L, x, dy, dwt, ws, N, H, W, Cin, Cout)
-    # the shipped knobs (conv.hip g_w1_*) are what the kernel above ran with, on every shape
+    # the shipped knobs (conv_wgrad.hip g_w1_*) are what the kernel above ran with, on every shape
     assert [lib.ewvit_conv2d_wgrad_1x1_config(i) for i in range(3)] == [256, 8, 2]
     prev = lib.ewvit_conv2d_set_wgrad_1x1(0, 0, 0)       # generic kernel; the other knobs kept
     try:
