@@ -36,27 +36,6 @@ template <int DT> struct Raw8;
 template <> struct Raw8<EWVIT_BF16> { uint4 q; };
 template <> struct Raw8<EWVIT_F32> { float4 a, b; };
 
-// NT: the non-temporal hint (global_load / global_store ... nt) on the ReLU instantiations (the
-// MWT's BatchNorms over 0.2-2.4 M-row maps, streamed once per pass) — compiled in only with
-// EWVIT_MWT_NT=1: measured a net loss with the other MWT hints (common.h)
-typedef unsigned bn_v4u __attribute__((ext_vector_type(4)));
-template <bool NT>
-__device__ __forceinline__ uint4 ldq16(const void *p) {
-  if constexpr (NT && EWVIT_MWT_NT) {
-    const bn_v4u v = __builtin_nontemporal_load(reinterpret_cast<const bn_v4u *>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-  } else {
-    return *reinterpret_cast<const uint4 *>(p);
-  }
-}
-template <bool NT>
-__device__ __forceinline__ void stq16(void *p, uint4 v) {
-  if constexpr (NT && EWVIT_MWT_NT) {
-    __builtin_nontemporal_store(bn_v4u{v.x, v.y, v.z, v.w}, reinterpret_cast<bn_v4u *>(p));
-  } else {
-    *reinterpret_cast<uint4 *>(p) = v;
-  }
-}
 template <int DT, bool NT = false>
 __device__ __forceinline__ Raw8<DT> ldraw(const void *p, int64_t i) {
   Raw8<DT> r;
@@ -84,51 +63,15 @@ __device__ __forceinline__ void unpack(const Raw8<DT> &r, float (&v)[8]) {
   }
 }
 
-template <int DT>
-__device__ __forceinline__ void ld8(const void *p, int64_t i, float (&v)[8]) {
-  if (DT == EWVIT_BF16) {
-    const uint4 q = *reinterpret_cast<const uint4 *>(reinterpret_cast<const bf16_t *>(p) + i);
-    const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] = __uint_as_float(w[j] << 16);
-      v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-    }
-  } else {
-    const float4 *q = reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(p) + i);
-    const float4 a = q[0], b = q[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-}
-template <int DT, bool NT = false>
-__device__ __forceinline__ void st8(void *p, int64_t i, const float (&v)[8]) {
-  if (DT == EWVIT_BF16) {
-    unsigned w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = (unsigned)f2bf(v[2 * j]) | ((unsigned)f2bf(v[2 * j + 1]) << 16);
-    stq16<NT>(reinterpret_cast<bf16_t *>(p) + i, make_uint4(w[0], w[1], w[2], w[3]));
-  } else {
-    float *f = reinterpret_cast<float *>(p) + i;
-    stq16<NT>(f, make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])));
-    stq16<NT>(f + 4, make_uint4(__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])));
-  }
-}
-
 template <int ACT>
 __device__ __forceinline__ float act_fwd(float z) {
   if (ACT == 1) return z > 0.f ? z : 0.f;
   if (ACT == 2) return z * __builtin_amdgcn_rcpf(1.f + __expf(-z));   // v_rcp_f32 (1 ulp), not IEEE div
   return z;
 }
+// bn_act_grad (common.h): the one derivative every producer of backward statistics uses
 template <int ACT>
-__device__ __forceinline__ float act_grad(float z) {
-  if (ACT == 1) return z > 0.f ? 1.f : 0.f;
-  if (ACT == 2) {
-    const float s = __builtin_amdgcn_rcpf(1.f + __expf(-z));
-    return s * (1.f + z * (1.f - s));
-  }
-  return 1.f;
-}
+__device__ __forceinline__ float act_grad(float z) { return bn_act_grad(ACT, z); }
 
 // ---------------------------------------------------------------- geometry
 struct BnGeo {
@@ -194,12 +137,6 @@ static int64_t bn_rows_per_block(const BnGeo &g, int64_t M, int groups) {
     if (rpt < need) rpt = need;
   }
   return (int64_t)g.RG * rpt;
-}
-
-// workspace (floats): [groups][nrc][2C] partial sums | [groups][C] shifts
-static int64_t bn_ws_floats(int64_t M, int64_t C, int groups) {
-  const BnGeo g = bn_geo(C);
-  return (int64_t)groups * bn_nrc(g, M, groups) * 2 * C + (int64_t)groups * C;
 }
 
 // the batched walk of a (row group, channel vector) thread over rows r0+rg,
@@ -828,23 +765,131 @@ __global__ __launch_bounds__(256) void bn_act_squeeze_kernel(const void *__restr
 
 using namespace ewvit;
 
-// instantiate launch L(dtype, act) for the runtime (dtype, act) pair
-#define BN_DISPATCH(L)                                  \
-  do {                                                  \
-    if (dtype == EWVIT_BF16) {                          \
-      if (act == 0) L(EWVIT_BF16, 0);                   \
-      else if (act == 1) L(EWVIT_BF16, 1);              \
-      else L(EWVIT_BF16, 2);                            \
-    } else {                                            \
-      if (act == 0) L(EWVIT_F32, 0);                    \
-      else if (act == 1) L(EWVIT_F32, 1);               \
-      else L(EWVIT_F32, 2);                             \
-    }                                                   \
-  } while (0)
+// ---------------------------------------------------------------- host: plan, launches, checks
+// Launch geometry of every pass over [M][C] in `groups` statistics groups: the reduction passes
+// (statistics, backward sums) leave nrc partial rows per (channel chunk, group), rpc rows per
+// block; the elementwise passes (apply, dx) take rpb rows per block.
+struct BnPlan {
+  BnGeo geo;
+  int C, groups;
+  int64_t Mg;                 // rows per group
+  int nrc;
+  int64_t rpc, rpb;
+  dim3 rgrid, egrid, block;   // reduction / elementwise grid
+  int64_t part_floats() const { return (int64_t)groups * nrc * 2 * C; }   // [groups][nrc][2C]
+};
+
+static BnPlan bn_plan(int64_t M, int64_t C, int groups) {
+  BnPlan p;
+  p.geo = bn_geo(C);
+  p.C = (int)C;
+  p.groups = groups;
+  p.Mg = M / groups;
+  p.nrc = bn_nrc(p.geo, p.Mg, groups);
+  p.rpc = (p.Mg + p.nrc - 1) / p.nrc;
+  p.rpb = bn_rows_per_block(p.geo, p.Mg, groups);
+  p.rgrid = dim3(p.nrc, p.geo.nch, groups);
+  p.egrid = dim3((unsigned)((p.Mg + p.rpb - 1) / p.rpb), p.geo.nch, groups);
+  p.block = dim3(p.geo.threads);
+  return p;
+}
+
+static void bn_launch_stats(const BnPlan &p, int dtype, const void *x, float *part, float *shifts, hipStream_t s) {
+  by_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(bn_stats_kernel<dt()>, p.rgrid, p.block, 0, s, x, p.Mg, p.C, p.geo.CC8, p.geo.RG, p.rpc, part,
+                       shifts);
+  });
+}
+
+// the statistics an apply pass finalises and the books it keeps
+struct BnApply {
+  const float *part, *shifts;
+  int nrc, training;
+  const float *gamma, *beta;
+  float *running_mean, *running_var;
+  float momentum, eps;
+  float *save_mean, *save_invstd;
+  int64_t *counter;
+};
+
+// y = act(bn(x)); `drop`: the drop-path + skip tail (act 0); `coef`: no rows, the coefficients
+// only (one block per chunk and group — the bf16 ReLU instantiation, whose row loop never runs)
+static void bn_launch_apply(const BnPlan &p, int dtype, int act, const void *x, void *y, const BnApply &a,
+                            const BnDrop *drop, float *coef, hipStream_t s) {
+  auto go = [&](auto kern, dim3 grid, int64_t rpb) {
+    hipLaunchKernelGGL(kern, grid, p.block, 0, s, x, y, a.part, a.shifts, a.nrc, p.Mg, p.C, p.geo.CC8, p.geo.RG, rpb,
+                       a.training, a.gamma, a.beta, a.running_mean, a.running_var, a.momentum, a.eps, a.save_mean,
+                       a.save_invstd, a.counter, drop ? *drop : BnDrop(), coef);
+  };
+  if (coef) go(bn_apply_kernel<EWVIT_BF16, 1>, dim3(1u, p.geo.nch, p.groups), (int64_t)0);
+  else if (drop) by_dtype(dtype, [&](auto dt) { go(bn_apply_kernel<dt(), 0, true>, p.egrid, p.rpb); });
+  else by_dtype_act(dtype, act, [&](auto dt, auto ac) { go(bn_apply_kernel<dt(), ac()>, p.egrid, p.rpb); });
+}
+
+// a backward pass's inputs, and what becomes of dy on its way in: nothing (sc 0), SC 1 a factor
+// per frame (s = row_scale [M / HW], the drop-path tail: act 0 only), SC 2 the squeeze-excitation
+// terms dy * s + g (s, g [M / HW][C])
+struct BnBwd {
+  const void *dy, *x;
+  const float *mean, *invstd, *gamma, *beta;
+  int sc = 0;
+  const float *s = nullptr;
+  int HW = 1;
+  const float *g = nullptr;
+  void row_scale(const float *rs, int64_t hw) { sc = 1; s = rs; HW = (int)hw; }
+  void se_terms(const float *se_s, const float *se_g, int64_t hw) { sc = 2; s = se_s; HW = (int)hw; g = se_g; }
+};
+
+// the two backward kernel families, and go(K::get<dtype, act, SC>()) for the run-time (dtype,
+// act, sc): SC 1 exists for act 0 only
+struct BnReduceK {
+  template <int DT, int ACT, int SC> static auto get() { return bn_bwd_reduce_kernel<DT, ACT, SC>; }
+};
+struct BnDxK {
+  template <int DT, int ACT, int SC> static auto get() { return bn_bwd_dx_kernel<DT, ACT, SC>; }
+};
+template <typename K, typename Go>
+static void bn_bwd_select(int dtype, int act, int sc, Go &&go) {
+  if (sc == 1) by_dtype(dtype, [&](auto dt) { go(K::template get<dt(), 0, 1>()); });
+  else if (sc == 2) by_dtype_act(dtype, act, [&](auto dt, auto ac) { go(K::template get<dt(), ac(), 2>()); });
+  else by_dtype_act(dtype, act, [&](auto dt, auto ac) { go(K::template get<dt(), ac(), 0>()); });
+}
+
+static void bn_launch_bwd_reduce(const BnPlan &p, int dtype, int act, const BnBwd &b, float *part, hipStream_t s) {
+  bn_bwd_select<BnReduceK>(dtype, act, b.sc, [&](auto kern) {
+    hipLaunchKernelGGL(kern, p.rgrid, p.block, 0, s, b.dy, b.x, b.mean, b.invstd, b.gamma, b.beta, p.Mg, p.C,
+                       p.geo.CC8, p.geo.RG, p.rpc, part, b.s, b.HW, b.g);
+  });
+}
+
+static void bn_launch_bwd_dx(const BnPlan &p, int dtype, int act, const BnBwd &b, const float *part, int nrc, void *dx,
+                             float *dgamma, float *dbeta, int accumulate, hipStream_t s) {
+  bn_bwd_select<BnDxK>(dtype, act, b.sc, [&](auto kern) {
+    hipLaunchKernelGGL(kern, p.egrid, p.block, 0, s, b.dy, b.x, b.mean, b.invstd, b.gamma, b.beta, part, nrc, dx, p.Mg,
+                       p.C, p.geo.CC8, p.geo.RG, p.rpb, dgamma, dbeta, accumulate, b.s, b.HW, b.g);
+  });
+}
+
+// the argument checks the entry points share (nm: the entry's name; act / groups / HW: null where
+// the entry has none)
+static int bn_check(const char *nm, int64_t M, int64_t C, const int *act, const int *groups, const int64_t *HW) {
+  EWVIT_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 4096, "%s: C=%lld must be a multiple of 8, <= 4096", nm, (long long)C);
+  EWVIT_CHECK_ARG(!act || (*act >= 0 && *act <= 2), "%s: act=%d", nm, act ? *act : 0);
+  EWVIT_CHECK_ARG(!groups || (*groups >= 1 && *groups <= 65535 && M % *groups == 0),
+                  "%s: M=%lld not divisible into %d groups", nm, (long long)M, groups ? *groups : 0);
+  EWVIT_CHECK_ARG(!HW || (*HW > 0 && M % *HW == 0 && M < ((int64_t)1 << 31)), "%s: M=%lld rows of %lld", nm,
+                  (long long)M, (long long)(HW ? *HW : 0));
+  return 0;
+}
+static int bn_check_nrc(const char *nm, int nrc, int max) {
+  EWVIT_CHECK_ARG(nrc >= 1 && nrc <= max, "%s: %d partial rows", nm, nrc);
+  return 0;
+}
 
 extern "C" int64_t ewvit_bn_workspace(int64_t M, int64_t C, int groups) {
   if (groups < 1) groups = 1;
-  return bn_ws_floats(M / groups, C, groups) * (int64_t)sizeof(float);
+  // [groups][nrc][2C] partial sums | [groups][C] shifts
+  return (bn_plan(M, C, groups).part_floats() + (int64_t)groups * C) * (int64_t)sizeof(float);
 }
 
 extern "C" int ewvit_bn_fwd(const void *x, void *y, int dtype, int64_t M, int64_t C, const float *gamma,
@@ -852,36 +897,18 @@ extern "C" int ewvit_bn_fwd(const void *x, void *y, int dtype, int64_t M, int64_
                             float momentum, float eps, int act, float *save_mean, float *save_invstd,
                             int groups, int64_t *num_batches_tracked, float *workspace, void *stream) {
   EWVIT_CHECK_ARG(x && y && workspace && dtype_ok(dtype), "bn_fwd: bad args");
-  EWVIT_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 4096, "bn_fwd: C=%lld must be a multiple of 8, <= 4096", (long long)C);
-  EWVIT_CHECK_ARG(act >= 0 && act <= 2, "bn_fwd: act=%d", act);
+  if (int rc = bn_check("bn_fwd", M, C, &act, &groups, nullptr)) return rc;
   EWVIT_CHECK_ARG(training || (running_mean && running_var), "bn_fwd: eval needs running stats");
-  EWVIT_CHECK_ARG(groups >= 1 && groups <= 65535 && M % groups == 0, "bn_fwd: M=%lld not divisible into %d groups",
-                  (long long)M, groups);
   if (M == 0) return 0;
   if (!training) groups = 1;
   hipStream_t s = as_stream(stream);
-  const int64_t Mg = M / groups;
-  const BnGeo geo = bn_geo(C);
-  const int nrc = bn_nrc(geo, Mg, groups);
-  float *part = workspace, *shifts = workspace + (int64_t)groups * nrc * 2 * C;
-  if (training) {
-    const int64_t rpc = (Mg + nrc - 1) / nrc;
-    dim3 grid(nrc, geo.nch, groups);
-    if (dtype == EWVIT_BF16)
-      hipLaunchKernelGGL(bn_stats_kernel<EWVIT_BF16>, grid, dim3(geo.threads), 0, s, x, Mg, (int)C, geo.CC8, geo.RG,
-                         rpc, part, shifts);
-    else
-      hipLaunchKernelGGL(bn_stats_kernel<EWVIT_F32>, grid, dim3(geo.threads), 0, s, x, Mg, (int)C, geo.CC8, geo.RG,
-                         rpc, part, shifts);
-  }
-  const int64_t rpb = bn_rows_per_block(geo, Mg, groups);
-  dim3 agrid((unsigned)((Mg + rpb - 1) / rpb), geo.nch, groups);
-#define BN_APPLY(DTV, ACTV)                                                                                          \
-  hipLaunchKernelGGL((bn_apply_kernel<DTV, ACTV>), agrid, dim3(geo.threads), 0, s, x, y, part, shifts, nrc, Mg,     \
-                     (int)C, geo.CC8, geo.RG, rpb, training, gamma, beta, running_mean, running_var, momentum, eps, \
-                     save_mean, save_invstd, num_batches_tracked)
-  BN_DISPATCH(BN_APPLY);
-#undef BN_APPLY
+  const BnPlan p = bn_plan(M, C, groups);
+  float *part = workspace, *shifts = workspace + p.part_floats();
+  if (training) bn_launch_stats(p, dtype, x, part, shifts, s);
+  bn_launch_apply(p, dtype, act, x, y,
+                  {part, shifts, p.nrc, training, gamma, beta, running_mean, running_var, momentum, eps, save_mean,
+                   save_invstd, num_batches_tracked},
+                  nullptr, nullptr, s);
   return launch_status("bn_fwd");
 }
 
@@ -929,24 +956,13 @@ extern "C" int ewvit_bn_fwd_partials(const void *x, void *y, int dtype, int64_t 
                                      int64_t *num_batches_tracked, const float *part, const float *shifts, int nrc,
                                      int groups, void *stream) {
   EWVIT_CHECK_ARG(x && y && part && shifts && dtype_ok(dtype), "bn_fwd_partials: bad args");
-  EWVIT_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 4096, "bn_fwd_partials: C=%lld must be a multiple of 8, <= 4096",
-                  (long long)C);
-  EWVIT_CHECK_ARG(act >= 0 && act <= 2, "bn_fwd_partials: act=%d", act);
-  EWVIT_CHECK_ARG(nrc >= 1 && nrc <= 4096, "bn_fwd_partials: %d partial rows", nrc);
-  EWVIT_CHECK_ARG(groups >= 1 && groups <= 65535 && M % groups == 0, "bn_fwd_partials: M=%lld, %d groups",
-                  (long long)M, groups);
+  if (int rc = bn_check("bn_fwd_partials", M, C, &act, &groups, nullptr)) return rc;
+  if (int rc = bn_check_nrc("bn_fwd_partials", nrc, 4096)) return rc;
   if (M == 0) return 0;
-  hipStream_t s = as_stream(stream);
-  const BnGeo geo = bn_geo(C);
-  const int64_t Mg = M / groups;
-  const int64_t rpb = bn_rows_per_block(geo, Mg, groups);
-  dim3 agrid((unsigned)((Mg + rpb - 1) / rpb), geo.nch, groups);
-#define BN_APPLY(DTV, ACTV)                                                                                          \
-  hipLaunchKernelGGL((bn_apply_kernel<DTV, ACTV>), agrid, dim3(geo.threads), 0, s, x, y, part, shifts, nrc, Mg,     \
-                     (int)C, geo.CC8, geo.RG, rpb, 1, gamma, beta, running_mean, running_var, momentum, eps,        \
-                     save_mean, save_invstd, num_batches_tracked)
-  BN_DISPATCH(BN_APPLY);
-#undef BN_APPLY
+  bn_launch_apply(bn_plan(M, C, groups), dtype, act, x, y,
+                  {part, shifts, nrc, 1, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd,
+                   num_batches_tracked},
+                  nullptr, nullptr, as_stream(stream));
   return launch_status("bn_fwd_partials");
 }
 
@@ -960,15 +976,13 @@ extern "C" int ewvit_bn_coef(int64_t M, int64_t C, const float *gamma, const flo
                              int64_t *num_batches_tracked, const float *part, const float *shifts, int nrc, int groups,
                              float *coef, void *stream) {
   EWVIT_CHECK_ARG(part && shifts && coef, "bn_coef: bad args");
-  EWVIT_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 4096, "bn_coef: C=%lld must be a multiple of 8, <= 4096", (long long)C);
-  EWVIT_CHECK_ARG(nrc >= 1 && nrc <= 4096, "bn_coef: %d partial rows", nrc);
-  EWVIT_CHECK_ARG(groups >= 1 && groups <= 65535 && M > 0 && M % groups == 0, "bn_coef: M=%lld, %d groups",
-                  (long long)M, groups);
-  const BnGeo geo = bn_geo(C);
-  dim3 grid(1u, geo.nch, groups);
-  hipLaunchKernelGGL((bn_apply_kernel<EWVIT_BF16, 1>), grid, dim3(geo.threads), 0, as_stream(stream), nullptr, nullptr,
-                     part, shifts, nrc, M / groups, (int)C, geo.CC8, geo.RG, (int64_t)0, 1, gamma, beta, running_mean,
-                     running_var, momentum, eps, save_mean, save_invstd, num_batches_tracked, BnDrop(), coef);
+  if (int rc = bn_check("bn_coef", M, C, nullptr, &groups, nullptr)) return rc;
+  if (int rc = bn_check_nrc("bn_coef", nrc, 4096)) return rc;
+  EWVIT_CHECK_ARG(M > 0, "bn_coef: no rows");
+  bn_launch_apply(bn_plan(M, C, groups), EWVIT_BF16, 1, nullptr, nullptr,
+                  {part, shifts, nrc, 1, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd,
+                   num_batches_tracked},
+                  nullptr, coef, as_stream(stream));
   return launch_status("bn_coef");
 }
 
@@ -982,43 +996,26 @@ extern "C" int ewvit_bn_fwd_drop_add(const void *x, void *y, int dtype, int64_t 
                                      float keep_prob, uint64_t seed, const int64_t *seed_offset, float *scale_out,
                                      float *workspace, void *stream) {
   EWVIT_CHECK_ARG(x && y && skip && scale_out && dtype_ok(dtype), "bn_fwd_drop_add: bad args");
-  EWVIT_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 4096, "bn_fwd_drop_add: C=%lld must be a multiple of 8, <= 4096",
-                  (long long)C);
-  EWVIT_CHECK_ARG(HW > 0 && M % HW == 0 && M < ((int64_t)1 << 31), "bn_fwd_drop_add: M=%lld rows of %lld", (long long)M,
-                  (long long)HW);
+  if (int rc = bn_check("bn_fwd_drop_add", M, C, nullptr, nullptr, &HW)) return rc;
   EWVIT_CHECK_ARG(keep_prob > 0.f && keep_prob <= 1.f, "bn_fwd_drop_add: keep_prob %g", (double)keep_prob);
   EWVIT_CHECK_ARG(part ? (shifts && nrc >= 1 && nrc <= 4096) : workspace != nullptr,
                   "bn_fwd_drop_add: partial statistics or a workspace");
   if (M == 0) return 0;
   hipStream_t s = as_stream(stream);
-  const BnGeo geo = bn_geo(C);
+  const BnPlan p = bn_plan(M, C, 1);
   if (!part) {
-    nrc = bn_nrc(geo, M, 1);
-    float *wpart = workspace, *wshift = workspace + (int64_t)nrc * 2 * C;
-    const int64_t rpc = (M + nrc - 1) / nrc;
-    dim3 grid(nrc, geo.nch, 1);
-    if (dtype == EWVIT_BF16)
-      hipLaunchKernelGGL(bn_stats_kernel<EWVIT_BF16>, grid, dim3(geo.threads), 0, s, x, M, (int)C, geo.CC8, geo.RG,
-                         rpc, wpart, wshift);
-    else
-      hipLaunchKernelGGL(bn_stats_kernel<EWVIT_F32>, grid, dim3(geo.threads), 0, s, x, M, (int)C, geo.CC8, geo.RG,
-                         rpc, wpart, wshift);
-    part = wpart;
-    shifts = wshift;
+    nrc = p.nrc;
+    bn_launch_stats(p, dtype, x, workspace, workspace + p.part_floats(), s);
+    part = workspace;
+    shifts = workspace + p.part_floats();
   }
   BnDrop dr;
   dr.skip = skip; dr.keep = keep_prob; dr.seed = seed; dr.seed_offset = seed_offset; dr.scale_out = scale_out;
   dr.HW = (int)HW;
-  const int64_t rpb = bn_rows_per_block(geo, M, 1);
-  dim3 agrid((unsigned)((M + rpb - 1) / rpb), geo.nch, 1);
-  if (dtype == EWVIT_BF16)
-    hipLaunchKernelGGL((bn_apply_kernel<EWVIT_BF16, 0, true>), agrid, dim3(geo.threads), 0, s, x, y, part, shifts, nrc,
-                       M, (int)C, geo.CC8, geo.RG, rpb, 1, gamma, beta, running_mean, running_var, momentum, eps,
-                       save_mean, save_invstd, num_batches_tracked, dr);
-  else
-    hipLaunchKernelGGL((bn_apply_kernel<EWVIT_F32, 0, true>), agrid, dim3(geo.threads), 0, s, x, y, part, shifts, nrc,
-                       M, (int)C, geo.CC8, geo.RG, rpb, 1, gamma, beta, running_mean, running_var, momentum, eps,
-                       save_mean, save_invstd, num_batches_tracked, dr);
+  bn_launch_apply(p, dtype, 0, x, y,
+                  {part, shifts, nrc, 1, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd,
+                   num_batches_tracked},
+                  &dr, nullptr, s);
   return launch_status("bn_fwd_drop_add");
 }
 
@@ -1030,30 +1027,14 @@ extern "C" int ewvit_bn_bwd_scaled(const void *dy, const void *x, void *dx, int 
                                    int64_t HW, float *workspace, void *stream) {
   EWVIT_CHECK_ARG(dy && x && dx && save_mean && save_invstd && row_scale && workspace && dtype_ok(dtype),
                   "bn_bwd_scaled: bad args");
-  EWVIT_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 4096, "bn_bwd_scaled: C=%lld", (long long)C);
-  EWVIT_CHECK_ARG(HW > 0 && M % HW == 0 && M < ((int64_t)1 << 31), "bn_bwd_scaled: M=%lld rows of %lld", (long long)M,
-                  (long long)HW);
+  if (int rc = bn_check("bn_bwd_scaled", M, C, nullptr, nullptr, &HW)) return rc;
   if (M == 0) return 0;
   hipStream_t s = as_stream(stream);
-  const BnGeo geo = bn_geo(C);
-  const int nrc = bn_nrc(geo, M, 1);
-  const int64_t rpc = (M + nrc - 1) / nrc;
-  dim3 grid(nrc, geo.nch, 1);
-  const int64_t rpb = bn_rows_per_block(geo, M, 1);
-  dim3 dgrid((unsigned)((M + rpb - 1) / rpb), geo.nch, 1);
-  if (dtype == EWVIT_BF16) {
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<EWVIT_BF16, 0, 1>), grid, dim3(geo.threads), 0, s, dy, x, save_mean,
-                       save_invstd, gamma, beta, M, (int)C, geo.CC8, geo.RG, rpc, workspace, row_scale, (int)HW);
-    hipLaunchKernelGGL((bn_bwd_dx_kernel<EWVIT_BF16, 0, 1>), dgrid, dim3(geo.threads), 0, s, dy, x, save_mean,
-                       save_invstd, gamma, beta, workspace, nrc, dx, M, (int)C, geo.CC8, geo.RG, rpb, dgamma, dbeta, 0,
-                       row_scale, (int)HW);
-  } else {
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<EWVIT_F32, 0, 1>), grid, dim3(geo.threads), 0, s, dy, x, save_mean,
-                       save_invstd, gamma, beta, M, (int)C, geo.CC8, geo.RG, rpc, workspace, row_scale, (int)HW);
-    hipLaunchKernelGGL((bn_bwd_dx_kernel<EWVIT_F32, 0, 1>), dgrid, dim3(geo.threads), 0, s, dy, x, save_mean,
-                       save_invstd, gamma, beta, workspace, nrc, dx, M, (int)C, geo.CC8, geo.RG, rpb, dgamma, dbeta, 0,
-                       row_scale, (int)HW);
-  }
+  const BnPlan p = bn_plan(M, C, 1);
+  BnBwd b{dy, x, save_mean, save_invstd, gamma, beta};
+  b.row_scale(row_scale, HW);
+  bn_launch_bwd_reduce(p, dtype, 0, b, workspace, s);
+  bn_launch_bwd_dx(p, dtype, 0, b, workspace, p.nrc, dx, dgamma, dbeta, 0, s);
   return launch_status("bn_bwd_scaled");
 }
 
@@ -1067,28 +1048,14 @@ extern "C" int ewvit_bn_bwd_se(const void *dy, const void *x, void *dx, int dtyp
                                float *workspace, void *stream) {
   EWVIT_CHECK_ARG(dy && x && dx && save_mean && save_invstd && se_s && se_g && workspace && dtype_ok(dtype),
                   "bn_bwd_se: bad args");
-  EWVIT_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 4096, "bn_bwd_se: C=%lld", (long long)C);
-  EWVIT_CHECK_ARG(act >= 0 && act <= 2, "bn_bwd_se: act=%d", act);
-  EWVIT_CHECK_ARG(HW > 0 && M % HW == 0 && M < ((int64_t)1 << 31), "bn_bwd_se: M=%lld rows of %lld", (long long)M,
-                  (long long)HW);
+  if (int rc = bn_check("bn_bwd_se", M, C, &act, nullptr, &HW)) return rc;
   if (M == 0) return 0;
   hipStream_t s = as_stream(stream);
-  const BnGeo geo = bn_geo(C);
-  const int nrc = bn_nrc(geo, M, 1);
-  const int64_t rpc = (M + nrc - 1) / nrc;
-  dim3 grid(nrc, geo.nch, 1);
-  const int64_t rpb = bn_rows_per_block(geo, M, 1);
-  dim3 dgrid((unsigned)((M + rpb - 1) / rpb), geo.nch, 1);
-#define BN_SE(DTV, ACTV)                                                                                            \
-  do {                                                                                                              \
-    hipLaunchKernelGGL((bn_bwd_reduce_kernel<DTV, ACTV, 2>), grid, dim3(geo.threads), 0, s, dy, x, save_mean,      \
-                       save_invstd, gamma, beta, M, (int)C, geo.CC8, geo.RG, rpc, workspace, se_s, (int)HW, se_g);  \
-    hipLaunchKernelGGL((bn_bwd_dx_kernel<DTV, ACTV, 2>), dgrid, dim3(geo.threads), 0, s, dy, x, save_mean,         \
-                       save_invstd, gamma, beta, workspace, nrc, dx, M, (int)C, geo.CC8, geo.RG, rpb, dgamma, dbeta, \
-                       0, se_s, (int)HW, se_g);                                                                     \
-  } while (0)
-  BN_DISPATCH(BN_SE);
-#undef BN_SE
+  const BnPlan p = bn_plan(M, C, 1);
+  BnBwd b{dy, x, save_mean, save_invstd, gamma, beta};
+  b.se_terms(se_s, se_g, HW);
+  bn_launch_bwd_reduce(p, dtype, act, b, workspace, s);
+  bn_launch_bwd_dx(p, dtype, act, b, workspace, p.nrc, dx, dgamma, dbeta, 0, s);
   return launch_status("bn_bwd_se");
 }
 
@@ -1098,15 +1065,9 @@ int bn_bwd_dx_se_launch(const void *dy, const void *x, void *dx, int dtype, int6
                         const float *beta, const float *save_mean, const float *save_invstd, int act, float *dgamma,
                         float *dbeta, const float *se_s, const float *se_g, int64_t HW, const float *part, int nrc,
                         hipStream_t s) {
-  const BnGeo geo = bn_geo(C);
-  const int64_t rpb = bn_rows_per_block(geo, M, 1);
-  dim3 dgrid((unsigned)((M + rpb - 1) / rpb), geo.nch, 1);
-#define BN_SE_DX(DTV, ACTV)                                                                                          \
-  hipLaunchKernelGGL((bn_bwd_dx_kernel<DTV, ACTV, 2>), dgrid, dim3(geo.threads), 0, s, dy, x, save_mean, save_invstd, \
-                     gamma, beta, part, nrc, dx, M, (int)C, geo.CC8, geo.RG, rpb, dgamma, dbeta, 0, se_s, (int)HW,   \
-                     se_g)
-  BN_DISPATCH(BN_SE_DX);
-#undef BN_SE_DX
+  BnBwd b{dy, x, save_mean, save_invstd, gamma, beta};
+  b.se_terms(se_s, se_g, HW);
+  bn_launch_bwd_dx(bn_plan(M, C, 1), dtype, act, b, part, nrc, dx, dgamma, dbeta, 0, s);
   return launch_status("bn_se_bwd");
 }
 }  // namespace ewvit
@@ -1122,35 +1083,14 @@ extern "C" int ewvit_bn_bwd_partials(const void *dy, const void *x, void *dx, in
                                      const float *row_scale, int64_t HW, const float *part, int nrc, int groups,
                                      void *stream) {
   EWVIT_CHECK_ARG(dy && x && dx && save_mean && save_invstd && part && dtype_ok(dtype), "bn_bwd_partials: bad args");
-  EWVIT_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 4096, "bn_bwd_partials: C=%lld", (long long)C);
-  EWVIT_CHECK_ARG(act >= 0 && act <= 2 && !(row_scale && act), "bn_bwd_partials: act=%d (row_scale needs act 0)", act);
-  EWVIT_CHECK_ARG(nrc >= 1 && nrc <= 65535, "bn_bwd_partials: %d partial rows", nrc);
-  EWVIT_CHECK_ARG(!row_scale || (HW > 0 && M % HW == 0 && M < ((int64_t)1 << 31)), "bn_bwd_partials: M=%lld rows of %lld",
-                  (long long)M, (long long)HW);
-  EWVIT_CHECK_ARG(groups >= 1 && groups <= 65535 && M % groups == 0 && (groups == 1 || !row_scale),
-                  "bn_bwd_partials: %d groups", groups);
+  if (int rc = bn_check("bn_bwd_partials", M, C, &act, &groups, row_scale ? &HW : nullptr)) return rc;
+  EWVIT_CHECK_ARG(!(row_scale && act), "bn_bwd_partials: act=%d (row_scale needs act 0)", act);
+  if (int rc = bn_check_nrc("bn_bwd_partials", nrc, 65535)) return rc;
+  EWVIT_CHECK_ARG(groups == 1 || !row_scale, "bn_bwd_partials: row_scale needs one group, not %d groups", groups);
   if (M == 0) return 0;
-  hipStream_t s = as_stream(stream);
-  const BnGeo geo = bn_geo(C);
-  const int64_t Mg = M / groups;
-  const int64_t rpb = bn_rows_per_block(geo, Mg, groups);
-  dim3 dgrid((unsigned)((Mg + rpb - 1) / rpb), geo.nch, groups);
-  if (row_scale) {
-    if (dtype == EWVIT_BF16)
-      hipLaunchKernelGGL((bn_bwd_dx_kernel<EWVIT_BF16, 0, 1>), dgrid, dim3(geo.threads), 0, s, dy, x, save_mean,
-                         save_invstd, gamma, beta, part, nrc, dx, M, (int)C, geo.CC8, geo.RG, rpb, dgamma, dbeta, 0,
-                         row_scale, (int)HW);
-    else
-      hipLaunchKernelGGL((bn_bwd_dx_kernel<EWVIT_F32, 0, 1>), dgrid, dim3(geo.threads), 0, s, dy, x, save_mean,
-                         save_invstd, gamma, beta, part, nrc, dx, M, (int)C, geo.CC8, geo.RG, rpb, dgamma, dbeta, 0,
-                         row_scale, (int)HW);
-    return launch_status("bn_bwd_partials");
-  }
-#define BN_DX(DTV, ACTV)                                                                                              \
-  hipLaunchKernelGGL((bn_bwd_dx_kernel<DTV, ACTV>), dgrid, dim3(geo.threads), 0, s, dy, x, save_mean, save_invstd,   \
-                     gamma, beta, part, nrc, dx, Mg, (int)C, geo.CC8, geo.RG, rpb, dgamma, dbeta, 0)
-  BN_DISPATCH(BN_DX);
-#undef BN_DX
+  BnBwd b{dy, x, save_mean, save_invstd, gamma, beta};
+  if (row_scale) b.row_scale(row_scale, HW);
+  bn_launch_bwd_dx(bn_plan(M, C, groups), dtype, act, b, part, nrc, dx, dgamma, dbeta, 0, as_stream(stream));
   return launch_status("bn_bwd_partials");
 }
 
@@ -1158,28 +1098,17 @@ extern "C" int ewvit_bn_bwd_partials(const void *dy, const void *x, void *dx, in
 // nrc = ewvit_bn_bwd_reduce_rows(M, C, groups), for a consumer that forms dx itself.
 extern "C" int ewvit_bn_bwd_reduce_rows(int64_t M, int64_t C, int groups) {
   if (groups < 1 || M < 1 || C < 8 || C > 4096 || C % 8 || M % groups) return 0;
-  return bn_nrc(bn_geo(C), M / groups, groups);
+  return bn_plan(M, C, groups).nrc;
 }
 
 extern "C" int ewvit_bn_bwd_reduce(const void *dy, const void *x, int dtype, int64_t M, int64_t C, const float *gamma,
                                    const float *beta, const float *save_mean, const float *save_invstd, int act,
                                    int groups, float *part, void *stream) {
   EWVIT_CHECK_ARG(dy && x && save_mean && save_invstd && part && dtype_ok(dtype), "bn_bwd_reduce: bad args");
-  EWVIT_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 4096, "bn_bwd_reduce: C=%lld", (long long)C);
-  EWVIT_CHECK_ARG(act >= 0 && act <= 2, "bn_bwd_reduce: act=%d", act);
-  EWVIT_CHECK_ARG(groups >= 1 && groups <= 65535 && M % groups == 0, "bn_bwd_reduce: %d groups", groups);
+  if (int rc = bn_check("bn_bwd_reduce", M, C, &act, &groups, nullptr)) return rc;
   if (M == 0) return 0;
-  const int64_t Mg = M / groups;
-  const BnGeo geo = bn_geo(C);
-  const int nrc = bn_nrc(geo, Mg, groups);
-  const int64_t rpc = (Mg + nrc - 1) / nrc;
-  dim3 grid(nrc, geo.nch, groups);
-  hipStream_t s = as_stream(stream);
-#define BN_RED(DTV, ACTV)                                                                                           \
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<DTV, ACTV>), grid, dim3(geo.threads), 0, s, dy, x, save_mean,           \
-                     save_invstd, gamma, beta, Mg, (int)C, geo.CC8, geo.RG, rpc, part)
-  BN_DISPATCH(BN_RED);
-#undef BN_RED
+  bn_launch_bwd_reduce(bn_plan(M, C, groups), dtype, act, {dy, x, save_mean, save_invstd, gamma, beta}, part,
+                       as_stream(stream));
   return launch_status("bn_bwd_reduce");
 }
 
@@ -1188,29 +1117,13 @@ extern "C" int ewvit_bn_bwd(const void *dy, const void *x, void *dx, int dtype, 
                             const float *save_invstd, int act, float *dgamma, float *dbeta, int accumulate,
                             int groups, float *workspace, void *stream) {
   EWVIT_CHECK_ARG(dy && x && dx && save_mean && save_invstd && workspace && dtype_ok(dtype), "bn_bwd: bad args");
-  EWVIT_CHECK_ARG(C > 0 && C % 8 == 0 && C <= 4096, "bn_bwd: C=%lld must be a multiple of 8, <= 4096", (long long)C);
-  EWVIT_CHECK_ARG(act >= 0 && act <= 2, "bn_bwd: act=%d", act);
-  EWVIT_CHECK_ARG(groups >= 1 && groups <= 65535 && M % groups == 0, "bn_bwd: M=%lld not divisible into %d groups",
-                  (long long)M, groups);
+  if (int rc = bn_check("bn_bwd", M, C, &act, &groups, nullptr)) return rc;
   if (M == 0) return 0;
   hipStream_t s = as_stream(stream);
-  const int64_t Mg = M / groups;
-  const BnGeo geo = bn_geo(C);
-  const int nrc = bn_nrc(geo, Mg, groups);
-  const int64_t rpc = (Mg + nrc - 1) / nrc;
-  dim3 grid(nrc, geo.nch, groups);
-#define BN_RED(DTV, ACTV)                                                                                           \
-  hipLaunchKernelGGL((bn_bwd_reduce_kernel<DTV, ACTV>), grid, dim3(geo.threads), 0, s, dy, x, save_mean,           \
-                     save_invstd, gamma, beta, Mg, (int)C, geo.CC8, geo.RG, rpc, workspace)
-  BN_DISPATCH(BN_RED);
-#undef BN_RED
-  const int64_t rpb = bn_rows_per_block(geo, Mg, groups);
-  dim3 dgrid((unsigned)((Mg + rpb - 1) / rpb), geo.nch, groups);
-#define BN_DX(DTV, ACTV)                                                                                              \
-  hipLaunchKernelGGL((bn_bwd_dx_kernel<DTV, ACTV>), dgrid, dim3(geo.threads), 0, s, dy, x, save_mean, save_invstd,   \
-                     gamma, beta, workspace, nrc, dx, Mg, (int)C, geo.CC8, geo.RG, rpb, dgamma, dbeta, accumulate)
-  BN_DISPATCH(BN_DX);
-#undef BN_DX
+  const BnPlan p = bn_plan(M, C, groups);
+  const BnBwd b{dy, x, save_mean, save_invstd, gamma, beta};
+  bn_launch_bwd_reduce(p, dtype, act, b, workspace, s);
+  bn_launch_bwd_dx(p, dtype, act, b, workspace, p.nrc, dx, dgamma, dbeta, accumulate, s);
   return launch_status("bn_bwd");
 }
 
@@ -1228,12 +1141,10 @@ extern "C" int ewvit_bn_act_se_squeeze(const void *x, void *y, int dtype, int64_
   EWVIT_CHECK_ARG(act >= 0 && act <= 2 && nrc >= 1 && nrc <= 65535 && Csq >= 1 && Csq <= 4096,
                   "bn_act_se_squeeze: act=%d nrc=%d Csq=%lld", act, nrc, (long long)Csq);
   const dim3 grid((unsigned)N, (unsigned)((C + 63) / 64));
-  hipStream_t s = as_stream(stream);
-#define BN_SQ(DTV, ACTV)                                                                                             \
-  hipLaunchKernelGGL((bn_act_squeeze_kernel<DTV, ACTV>), grid, dim3(256), 0, s, x, y, part, shifts, nrc, (int)HW,   \
-                     (int)C, gamma, beta, running_mean, running_var, momentum, eps, save_mean, save_invstd,         \
-                     num_batches_tracked, 1.f / (float)HW, w1, (int)Csq, s0, hpart)
-  BN_DISPATCH(BN_SQ);
-#undef BN_SQ
+  by_dtype_act(dtype, act, [&](auto dt, auto ac) {
+    hipLaunchKernelGGL((bn_act_squeeze_kernel<dt(), ac()>), grid, dim3(256), 0, as_stream(stream), x, y, part, shifts,
+                       nrc, (int)HW, (int)C, gamma, beta, running_mean, running_var, momentum, eps, save_mean,
+                       save_invstd, num_batches_tracked, 1.f / (float)HW, w1, (int)Csq, s0, hpart);
+  });
   return launch_status("bn_act_se_squeeze");
 }

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <cstdio>
 #include <cstdarg>
+#include <type_traits>
 #include <utility>
 
 #include "../../include/ewvit.h"
@@ -95,6 +96,60 @@ __device__ __forceinline__ void store_dt(void *p, int64_t i, float v, int dt) {
     reinterpret_cast<bf16_t *>(p)[i] = f2bf(v);
 }
 
+// 16-byte accesses.  NT: the non-temporal hint (global_load / global_store ... nt) on BatchNorm's
+// ReLU instantiations (the MWT's BatchNorms over 0.2-2.4 M-row maps, streamed once per pass) —
+// compiled in only with EWVIT_MWT_NT=1: measured a net loss with the other MWT hints (above)
+typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
+template <bool NT>
+__device__ __forceinline__ uint4 ldq16(const void *p) {
+  if constexpr (NT && EWVIT_MWT_NT) {
+    const v4u_t v = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(p));
+    return make_uint4(v.x, v.y, v.z, v.w);
+  } else {
+    return *reinterpret_cast<const uint4 *>(p);
+  }
+}
+template <bool NT>
+__device__ __forceinline__ void stq16(void *p, uint4 v) {
+  if constexpr (NT && EWVIT_MWT_NT) {
+    __builtin_nontemporal_store(v4u_t{v.x, v.y, v.z, v.w}, reinterpret_cast<v4u_t *>(p));
+  } else {
+    *reinterpret_cast<uint4 *>(p) = v;
+  }
+}
+
+// 8 consecutive elements of dtype DT at element index i (16 B bf16 / 32 B f32, aligned to that)
+// <-> fp32 registers: what the channels-last elementwise kernels move per thread
+template <int DT>
+__device__ __forceinline__ void ld8(const void *p, int64_t i, float (&v)[8]) {
+  if constexpr (DT == EWVIT_BF16) {
+    const uint4 q = *reinterpret_cast<const uint4 *>(reinterpret_cast<const bf16_t *>(p) + i);
+    const unsigned w[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      v[2 * j] = __uint_as_float(w[j] << 16);
+      v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
+    }
+  } else {
+    const float4 *q = reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(p) + i);
+    const float4 a = q[0], b = q[1];
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+  }
+}
+template <int DT, bool NT = false>
+__device__ __forceinline__ void st8(void *p, int64_t i, const float (&v)[8]) {
+  if constexpr (DT == EWVIT_BF16) {
+    unsigned w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] = (unsigned)f2bf(v[2 * j]) | ((unsigned)f2bf(v[2 * j + 1]) << 16);
+    stq16<NT>(reinterpret_cast<bf16_t *>(p) + i, make_uint4(w[0], w[1], w[2], w[3]));
+  } else {
+    float *f = reinterpret_cast<float *>(p) + i;
+    stq16<NT>(f, make_uint4(__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])));
+    stq16<NT>(f + 4, make_uint4(__float_as_uint(v[4]), __float_as_uint(v[5]), __float_as_uint(v[6]), __float_as_uint(v[7])));
+  }
+}
+
 // ---------------------------------------------------------------- RNG
 // Counter-based hash (splitmix64 finaliser) for dropout: keep(seed, i) is a
 // pure function, so backward regenerates the forward mask without storing it.
@@ -156,8 +211,8 @@ __device__ __forceinline__ float gelu_erf_grad(float x) {
 }
 
 // derivative of a BatchNorm's activation at its pre-activation z (act 1 ReLU, 2 SiLU, else
-// identity) — the same operations as batchnorm.hip's act_grad, so producers that sum the
-// backward statistics in their epilogue round exactly as bn_bwd_reduce_kernel would
+// identity) — the one definition batchnorm.hip's and se.hip's passes and the producers that sum
+// the backward statistics in their epilogue share, so all of them round alike
 __device__ __forceinline__ float bn_act_grad(int act, float z) {
   if (act == 1) return z > 0.f ? 1.f : 0.f;
   if (act == 2) {
@@ -183,6 +238,28 @@ struct BnBwdStats {
 };
 
 inline bool dtype_ok(int dt) { return dt == EWVIT_F32 || dt == EWVIT_BF16; }
+
+// ---------------------------------------------------------------- host dispatch
+// The run-time dtype (checked: dtype_ok) and BatchNorm activation (checked: 0 / 1 / 2) as
+// compile-time tags: f is called with std::integral_constant values, so a launch names its
+// kernel template once —
+//   by_dtype_act(dtype, act, [&](auto dt, auto a) { hipLaunchKernelGGL((k<dt(), a()>), ...); });
+// Only the kernels a lambda names are instantiated, for the tags its dispatcher passes.
+template <typename F>
+inline void by_dtype(int dtype, F &&f) {
+  if (dtype == EWVIT_BF16) f(std::integral_constant<int, EWVIT_BF16>{});
+  else f(std::integral_constant<int, EWVIT_F32>{});
+}
+template <typename F>
+inline void by_act(int act, F &&f) {
+  if (act == 0) f(std::integral_constant<int, 0>{});
+  else if (act == 1) f(std::integral_constant<int, 1>{});
+  else f(std::integral_constant<int, 2>{});
+}
+template <typename F>
+inline void by_dtype_act(int dtype, int act, F &&f) {
+  by_dtype(dtype, [&](auto dt) { by_act(act, [&](auto a) { f(dt, a); }); });
+}
 
 // workgroup cap of the big-grid launches (abi.hip, ewvit_set_grid_cap); 0 = none; per host thread
 extern thread_local int g_grid_cap;

@@ -939,6 +939,57 @@ static DwShape mk(int64_t N, int64_t H, int64_t W, int64_t C, int stride, int pa
   return s;
 }
 
+// input and output both within the row kernels' 32-bit buffer offsets
+static bool dw_buf_fits(const DwShape &s) {
+  return dw_bufok((int64_t)s.N * s.H * s.W * s.C) && dw_bufok((int64_t)s.N * s.Ho * s.Wo * s.C);
+}
+
+// dw_row4_kernel<MODE, act, WG, SE>: MODE 1 the stride-1 forward (no act, no WG), MODE 2 the stride-1
+// backward for the producing BatchNorm's act, with the weight gradient (WG) and the SE fold (SE, WG
+// only); its grid: 32 rows x DW_NQ channel quads per block
+using DwRow4 = decltype(&dw_row4_kernel<1, 0, false, false>);
+static DwRow4 dw_row4_select(int mode, int act, bool wg, bool se) {
+  DwRow4 k = dw_row4_kernel<1, 0, false>;
+  if (mode == 2)
+    by_act(act, [&](auto a) {
+      k = !wg ? dw_row4_kernel<2, a(), false> : se ? dw_row4_kernel<2, a(), true, true> : dw_row4_kernel<2, a(), true>;
+    });
+  return k;
+}
+static dim3 dw_row4_grid(int64_t n, int64_t C) { return dim3((unsigned)n, (unsigned)((C / 4 + DW_NQ - 1) / DW_NQ)); }
+
+// the backward statistics of the BatchNorm(+act) whose output the conv read
+static BnBwdStats dw_bn_stats(float *part, const void *bx, const float *mean, const float *invstd, const float *gamma,
+                              const float *beta, int act) {
+  BnBwdStats b;
+  b.part = part; b.x = (const bf16_t *)bx; b.mean = mean; b.invstd = invstd; b.gamma = gamma; b.beta = beta;
+  b.act = act;
+  return b;
+}
+
+// dW [n] (= or +=) the sum of the `slabs` slabs in ws: queued (defer: reduce_jobs.h) or launched
+static int dw_wgrad_finish(const char *what, float *ws, float *dw, int64_t n, int slabs, int accumulate, bool defer,
+                           hipStream_t st) {
+  if (defer) {
+    RedJob j;
+    j.kind = 2; j.part = ws; j.dw = dw; j.n = n; j.splits = slabs; j.accumulate = accumulate;
+    reduce_defer(st, j);
+    return 0;
+  }
+  hipLaunchKernelGGL(dw_bwd_weight_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, ws, dw, n, slabs,
+                     accumulate);
+  return launch_status(what);
+}
+
+// a per-row bf16 kernel over `rows` rows of `s`: 256 / (C / 8) rows per block, whole rows (segs = 1)
+template <typename K>
+static void dw_launch_rows(K kern, int64_t rows, const DwShape &s, const void *in, const float *w, void *out,
+                           hipStream_t st) {
+  const int rpb = 256 / (s.C / 8), segs = 1;
+  hipLaunchKernelGGL(kern, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(256), 0, st, (const bf16_t *)in, w,
+                     (bf16_t *)out, s, rpb, segs);
+}
+
 // The row kernels walk whole output rows (segs = 1).  Measured and removed: column segments
 // per row for the 7^2 / 14^2 maps (2682 vs 2703 frames/s: one more 3x3 window fill per
 // segment) and a per-pixel kernel for them (SFE piece 14.29-14.32 -> 15.09-15.12 ms: the 9 tap
@@ -949,23 +1000,14 @@ extern "C" int ewvit_dwconv3x3_fwd(const void *x, const float *w, void *y, int64
   EWVIT_CHECK_ARG(x && w && y && dtype_ok(dtype), "dwconv3x3_fwd: bad args");
   DwShape s = mk(N, H, W, C, stride, pad);
   if (int rc = check_shape(s, "dwconv3x3_fwd")) return rc;
-  const bool buf = dw_bufok((int64_t)s.N * s.H * s.W * s.C) && dw_bufok((int64_t)s.N * s.Ho * s.Wo * s.C);
-  if (dtype == EWVIT_BF16 && s.C / 8 <= 256 && (s.stride == 1 || s.stride == 2) && buf) {
-    const int rpb = 256 / (s.C / 8), segs = 1;
-    dim3 grid((unsigned)(((int64_t)s.N * s.Ho + rpb - 1) / rpb));
-    if (s.stride == 1)
-      hipLaunchKernelGGL((dw_row_bf16_kernel<1, false>), grid, dim3(256), 0, as_stream(stream),
-                         (const bf16_t *)x, w, (bf16_t *)y, s, rpb, segs);
-    else
-      hipLaunchKernelGGL((dw_row_bf16_kernel<2, false>), grid, dim3(256), 0, as_stream(stream),
-                         (const bf16_t *)x, w, (bf16_t *)y, s, rpb, segs);
+  hipStream_t st = as_stream(stream);
+  if (dtype == EWVIT_BF16 && s.C / 8 <= 256 && (s.stride == 1 || s.stride == 2) && dw_buf_fits(s)) {
+    dw_launch_rows(s.stride == 1 ? dw_row_bf16_kernel<1, false> : dw_row_bf16_kernel<2, false>, (int64_t)s.N * s.Ho, s,
+                   x, w, y, st);
   } else {
     const int64_t total = (int64_t)s.N * s.Ho * s.Wo * (s.C / 8);
     dim3 grid((unsigned)((total + 255) / 256));
-    if (dtype == EWVIT_BF16)
-      hipLaunchKernelGGL(dw_fwd_kernel<EWVIT_BF16>, grid, dim3(256), 0, as_stream(stream), x, w, y, s);
-    else
-      hipLaunchKernelGGL(dw_fwd_kernel<EWVIT_F32>, grid, dim3(256), 0, as_stream(stream), x, w, y, s);
+    by_dtype(dtype, [&](auto dt) { hipLaunchKernelGGL(dw_fwd_kernel<dt()>, grid, dim3(256), 0, st, x, w, y, s); });
   }
   return launch_status("dwconv3x3_fwd");
 }
@@ -975,29 +1017,21 @@ extern "C" int ewvit_dwconv3x3_bwd_data(const void *dy, const float *w, void *dx
   EWVIT_CHECK_ARG(dy && w && dx && dtype_ok(dtype), "dwconv3x3_bwd_data: bad args");
   DwShape s = mk(N, H, W, C, stride, pad);
   if (int rc = check_shape(s, "dwconv3x3_bwd_data")) return rc;
-  const bool buf = dw_bufok((int64_t)s.N * s.H * s.W * s.C) && dw_bufok((int64_t)s.N * s.Ho * s.Wo * s.C);
-  if (dtype == EWVIT_BF16 && s.stride == 1 && s.pad == 1 && s.C / 8 <= 256 && buf) {
+  hipStream_t st = as_stream(stream);
+  const bool row = dtype == EWVIT_BF16 && s.pad == 1 && s.C / 8 <= 256 && dw_buf_fits(s);
+  if (row && s.stride == 1) {
     // input gradient of a stride-1 pad-1 conv = stride-1 pad-1 conv of dy with the rotated kernel
     DwShape t = s;
     t.H = s.Ho; t.W = s.Wo; t.Ho = s.H; t.Wo = s.W;
-    const int rpb = 256 / (s.C / 8), segs = 1;
-    dim3 grid((unsigned)(((int64_t)t.N * t.Ho + rpb - 1) / rpb));
-    hipLaunchKernelGGL((dw_row_bf16_kernel<1, true>), grid, dim3(256), 0, as_stream(stream),
-                       (const bf16_t *)dy, w, (bf16_t *)dx, t, rpb, segs);
-  } else if (dtype == EWVIT_BF16 && s.stride == 2 && s.pad == 1 && s.C / 8 <= 256 && buf && s.Ho == (s.H + 1) / 2 &&
-             s.Wo == (s.W + 1) / 2) {
+    dw_launch_rows(dw_row_bf16_kernel<1, true>, (int64_t)t.N * t.Ho, t, dy, w, dx, st);
+  } else if (row && s.stride == 2 && s.Ho == (s.H + 1) / 2 && s.Wo == (s.W + 1) / 2) {
     // stride 2: dx rows in column pairs (dw_row_s2_bwd_kernel)
-    const int rpb = 256 / (s.C / 8), segs = 1;
-    dim3 grid((unsigned)(((int64_t)s.N * s.H + rpb - 1) / rpb));
-    hipLaunchKernelGGL(dw_row_s2_bwd_kernel, grid, dim3(256), 0, as_stream(stream), (const bf16_t *)dy, w,
-                       (bf16_t *)dx, s, rpb, segs);
+    dw_launch_rows(dw_row_s2_bwd_kernel, (int64_t)s.N * s.H, s, dy, w, dx, st);
   } else {
     const int64_t total = (int64_t)s.N * s.H * s.W * (s.C / 8);
     dim3 grid((unsigned)((total + 255) / 256));
-    if (dtype == EWVIT_BF16)
-      hipLaunchKernelGGL(dw_bwd_data_kernel<EWVIT_BF16>, grid, dim3(256), 0, as_stream(stream), dy, w, dx, s);
-    else
-      hipLaunchKernelGGL(dw_bwd_data_kernel<EWVIT_F32>, grid, dim3(256), 0, as_stream(stream), dy, w, dx, s);
+    by_dtype(dtype,
+             [&](auto dt) { hipLaunchKernelGGL(dw_bwd_data_kernel<dt()>, grid, dim3(256), 0, st, dy, w, dx, s); });
   }
   return launch_status("dwconv3x3_bwd_data");
 }
@@ -1005,7 +1039,6 @@ extern "C" int ewvit_dwconv3x3_bwd_data(const void *dy, const float *w, void *dx
 // partial rows the BatchNorm-sum forms below leave (one per 32 output rows n*Ho + ho of
 // the output they store), or 0 when the shape does not take them (bf16 only, pad 1,
 // stride 1 | 2 forward / stride 1 input gradient, C % 8 == 0)
-
 extern "C" int64_t ewvit_dwconv3x3_bn_rows(int64_t N, int64_t H, int64_t W, int64_t C, int stride, int bwd) {
   if (N <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || C > 65536 * 8 || (stride != 1 && stride != 2) ||
       (bwd && stride != 1) || !dw_bufok(N * H * W * C))
@@ -1014,27 +1047,33 @@ extern "C" int64_t ewvit_dwconv3x3_bn_rows(int64_t N, int64_t H, int64_t W, int6
   return (N * Ho + 31) / 32;
 }
 
+// the shape of a BatchNorm-sum form (pad 1) and its partial rows, or EINVAL
+static int dw_bn_shape(const char *nm, int64_t N, int64_t H, int64_t W, int64_t C, int stride, int bwd, DwShape *s,
+                       int64_t *nrc) {
+  *nrc = ewvit_dwconv3x3_bn_rows(N, H, W, C, stride, bwd);
+  EWVIT_CHECK_ARG(*nrc > 0 && *nrc < 65536, "%s: shape not supported", nm);
+  *s = mk(N, H, W, C, stride, 1);
+  return check_shape(*s, nm);
+}
+
 // forward + the BatchNorm statistics of y (shifted sums, ewvit_bn_fwd_partials): part
 // [ewvit_dwconv3x3_bn_rows(..., 0)][2C], shift_out [C] (= shift, or zeros)
 extern "C" int ewvit_dwconv3x3_fwd_bn(const void *x, const float *w, void *y, int64_t N, int64_t H, int64_t W,
                                       int64_t C, int stride, const float *shift, float *part, float *shift_out,
                                       void *stream) {
   EWVIT_CHECK_ARG(x && w && y && part && shift_out, "dwconv3x3_fwd_bn: null pointer");
-  const int64_t nrc = ewvit_dwconv3x3_bn_rows(N, H, W, C, stride, 0);
-  EWVIT_CHECK_ARG(nrc > 0 && nrc < 65536, "dwconv3x3_fwd_bn: shape not supported");
-  DwShape s = mk(N, H, W, C, stride, 1);
-  if (int rc = check_shape(s, "dwconv3x3_fwd_bn")) return rc;
+  DwShape s;
+  int64_t nrc;
+  if (int rc = dw_bn_shape("dwconv3x3_fwd_bn", N, H, W, C, stride, 0, &s, &nrc)) return rc;
   DwBnFwd f;
   f.part = part; f.shift = shift; f.shift_out = shift_out;
   BnBwdStats b;
-  if (stride == 1) {
-    hipLaunchKernelGGL((dw_row4_kernel<1, 0, false>), dim3((unsigned)nrc, (unsigned)((C / 4 + DW_NQ - 1) / DW_NQ)),
-                       dim3(DW_THREADS), 0,
+  if (stride == 1)
+    hipLaunchKernelGGL(dw_row4_select(1, 0, false, false), dw_row4_grid(nrc, C), dim3(DW_THREADS), 0,
                        as_stream(stream), (const bf16_t *)x, nullptr, w, (bf16_t *)y, s, f, b, nullptr, DwSe());
-    return launch_status("dwconv3x3_fwd_bn");
-  }
-  hipLaunchKernelGGL((dw_row_bn_kernel<2, false, 1, 0>), dim3((unsigned)nrc, (unsigned)((C / 8 + 7) / 8)), dim3(256), 0,
-                     as_stream(stream), (const bf16_t *)x, w, (bf16_t *)y, s, f, b);
+  else
+    hipLaunchKernelGGL((dw_row_bn_kernel<2, false, 1, 0>), dim3((unsigned)nrc, (unsigned)((C / 8 + 7) / 8)), dim3(256),
+                       0, as_stream(stream), (const bf16_t *)x, w, (bf16_t *)y, s, f, b);
   return launch_status("dwconv3x3_fwd_bn");
 }
 
@@ -1048,17 +1087,12 @@ extern "C" int ewvit_dwconv3x3_bwd_data_bn(const void *dy, const float *w, void 
                                            void *stream) {
   EWVIT_CHECK_ARG(dy && w && dx && bx && mean && invstd && part && act >= 0 && act <= 2,
                   "dwconv3x3_bwd_data_bn: bad args");
-  const int64_t nrc = ewvit_dwconv3x3_bn_rows(N, H, W, C, 1, 1);
-  EWVIT_CHECK_ARG(nrc > 0 && nrc < 65536, "dwconv3x3_bwd_data_bn: shape not supported");
-  DwShape s = mk(N, H, W, C, 1, 1);
-  if (int rc = check_shape(s, "dwconv3x3_bwd_data_bn")) return rc;
-  DwBnFwd f;
-  BnBwdStats b;
-  b.part = part; b.x = (const bf16_t *)bx; b.mean = mean; b.invstd = invstd; b.gamma = gamma; b.beta = beta;
-  b.act = act;
-  auto kern = act == 2 ? dw_row4_kernel<2, 2, false> : act == 1 ? dw_row4_kernel<2, 1, false> : dw_row4_kernel<2, 0, false>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nrc, (unsigned)((C / 4 + DW_NQ - 1) / DW_NQ)), dim3(DW_THREADS), 0,
-                     as_stream(stream), (const bf16_t *)dy, nullptr, w, (bf16_t *)dx, s, f, b, nullptr, DwSe());
+  DwShape s;
+  int64_t nrc;
+  if (int rc = dw_bn_shape("dwconv3x3_bwd_data_bn", N, H, W, C, 1, 1, &s, &nrc)) return rc;
+  hipLaunchKernelGGL(dw_row4_select(2, act, false, false), dw_row4_grid(nrc, C), dim3(DW_THREADS), 0,
+                     as_stream(stream), (const bf16_t *)dy, nullptr, w, (bf16_t *)dx, s, DwBnFwd(),
+                     dw_bn_stats(part, bx, mean, invstd, gamma, beta, act), nullptr, DwSe());
   return launch_status("dwconv3x3_bwd_data_bn");
 }
 
@@ -1068,9 +1102,23 @@ extern "C" int64_t ewvit_dwconv3x3_bwd_fused_workspace(int64_t N, int64_t H, int
   return nrc * C * 9 * (int64_t)sizeof(float);
 }
 
-// the stride-1 pad-1 backward in one pass (dw_row4_kernel WG): dx, the producing BatchNorm's
-// backward sums (as ewvit_dwconv3x3_bwd_data_bn: part [ewvit_dwconv3x3_bn_rows(..., 1)][2C])
-// and dW [C][9] (= or += with accumulate) from x, the conv's bf16 input
+// the stride-1 pad-1 backward in one pass (dw_row4_kernel WG; SE fold: `e`); defer: reduce_take_defer()
+static int dw_bwd_fused(const char *nm, const char *nm_reduce, bool defer, const void *dy, const float *w, void *dx,
+                        const void *x, float *dw, int accumulate, int64_t N, int64_t H, int64_t W, int64_t C,
+                        const BnBwdStats &b, float *workspace, const DwSe *e, hipStream_t st) {
+  DwShape s;
+  int64_t nrc;
+  if (int rc = dw_bn_shape(nm, N, H, W, C, 1, 1, &s, &nrc)) return rc;
+  hipLaunchKernelGGL(dw_row4_select(2, b.act, true, e != nullptr), dw_row4_grid(nrc, C), dim3(DW_THREADS), 0, st,
+                     (const bf16_t *)dy, (const bf16_t *)x, w, (bf16_t *)dx, s, DwBnFwd(), b, workspace,
+                     e ? *e : DwSe());
+  if (int rc = launch_status(nm)) return rc;
+  return dw_wgrad_finish(nm_reduce, workspace, dw, C * 9, (int)nrc, accumulate, defer, st);
+}
+
+// dx, the producing BatchNorm's backward sums (as ewvit_dwconv3x3_bwd_data_bn: part
+// [ewvit_dwconv3x3_bn_rows(..., 1)][2C]) and dW [C][9] (= or += with accumulate) from x, the
+// conv's bf16 input
 extern "C" int ewvit_dwconv3x3_bwd_fused(const void *dy, const float *w, void *dx, const void *x, float *dw,
                                          int accumulate, int64_t N, int64_t H, int64_t W, int64_t C, const void *bx,
                                          const float *mean, const float *invstd, const float *gamma,
@@ -1078,29 +1126,9 @@ extern "C" int ewvit_dwconv3x3_bwd_fused(const void *dy, const float *w, void *d
   const bool defer_mark = reduce_take_defer();      // (reduce_jobs.h; consumed by every call)
   EWVIT_CHECK_ARG(dy && w && dx && x && dw && bx && mean && invstd && part && workspace && act >= 0 && act <= 2,
                   "dwconv3x3_bwd_fused: bad args");
-  const int64_t nrc = ewvit_dwconv3x3_bn_rows(N, H, W, C, 1, 1);
-  EWVIT_CHECK_ARG(nrc > 0 && nrc < 65536, "dwconv3x3_bwd_fused: shape not supported");
-  DwShape s = mk(N, H, W, C, 1, 1);
-  if (int rc = check_shape(s, "dwconv3x3_bwd_fused")) return rc;
-  BnBwdStats b;
-  b.part = part; b.x = (const bf16_t *)bx; b.mean = mean; b.invstd = invstd; b.gamma = gamma; b.beta = beta;
-  b.act = act;
-  hipStream_t st = as_stream(stream);
-  DwBnFwd f;
-  auto kern = act == 2 ? dw_row4_kernel<2, 2, true> : act == 1 ? dw_row4_kernel<2, 1, true> : dw_row4_kernel<2, 0, true>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nrc, (unsigned)((C / 4 + DW_NQ - 1) / DW_NQ)), dim3(DW_THREADS), 0, st,
-                     (const bf16_t *)dy, (const bf16_t *)x, w, (bf16_t *)dx, s, f, b, workspace, DwSe());
-  if (int rc = launch_status("dwconv3x3_bwd_fused")) return rc;
-  const int64_t n = C * 9;
-  if (defer_mark) {                 // the slab sum runs in front of a later weight-gradient launch
-    RedJob j;
-    j.kind = 2; j.part = workspace; j.dw = dw; j.n = n; j.splits = (int)nrc; j.accumulate = accumulate;
-    reduce_defer(st, j);
-    return 0;
-  }
-  hipLaunchKernelGGL(dw_bwd_weight_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, workspace, dw, n,
-                     (int)nrc, accumulate);
-  return launch_status("dwconv3x3_bwd_fused reduce");
+  return dw_bwd_fused("dwconv3x3_bwd_fused", "dwconv3x3_bwd_fused reduce", defer_mark, dy, w, dx, x, dw, accumulate, N,
+                      H, W, C, dw_bn_stats(part, bx, mean, invstd, gamma, beta, act), workspace, nullptr,
+                      as_stream(stream));
 }
 
 // ewvit_dwconv3x3_bwd_fused with the BatchNorm(+act) + squeeze-excitation backward of the conv's
@@ -1117,41 +1145,19 @@ extern "C" int ewvit_dwconv3x3_bwd_fused_se(const void *dy, const float *w, void
   EWVIT_CHECK_ARG(dy && w && dx && x && dw && bx && mean && invstd && part && workspace && act >= 0 && act <= 2 &&
                       z && se_mean && se_invstd && se_row && se_s && se_g && se_act >= 0 && se_act <= 2,
                   "dwconv3x3_bwd_fused_se: bad args");
-  const int64_t nrc = ewvit_dwconv3x3_bn_rows(N, H, W, C, 1, 1);
-  EWVIT_CHECK_ARG(nrc > 0 && nrc < 65536, "dwconv3x3_bwd_fused_se: shape not supported");
-  DwShape s = mk(N, H, W, C, 1, 1);
-  if (int rc = check_shape(s, "dwconv3x3_bwd_fused_se")) return rc;
-  BnBwdStats b;
-  b.part = part; b.x = (const bf16_t *)bx; b.mean = mean; b.invstd = invstd; b.gamma = gamma; b.beta = beta;
-  b.act = act;
   DwSe e;
   e.z = (const bf16_t *)z; e.mean = se_mean; e.invstd = se_invstd; e.gamma = se_gamma; e.beta = se_beta;
   e.row = se_row; e.s = se_s; e.g = se_g; e.n = (float)(N * H * W); e.act = se_act;
-  hipStream_t st = as_stream(stream);
-  DwBnFwd f;
-  auto kern = act == 2 ? dw_row4_kernel<2, 2, true, true> : act == 1 ? dw_row4_kernel<2, 1, true, true>
-                                                                   : dw_row4_kernel<2, 0, true, true>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)nrc, (unsigned)((C / 4 + DW_NQ - 1) / DW_NQ)), dim3(DW_THREADS), 0, st,
-                     (const bf16_t *)dy, (const bf16_t *)x, w, (bf16_t *)dx, s, f, b, workspace, e);
-  if (int rc = launch_status("dwconv3x3_bwd_fused_se")) return rc;
-  const int64_t n = C * 9;
-  if (defer_mark) {
-    RedJob j;
-    j.kind = 2; j.part = workspace; j.dw = dw; j.n = n; j.splits = (int)nrc; j.accumulate = accumulate;
-    reduce_defer(st, j);
-    return 0;
-  }
-  hipLaunchKernelGGL(dw_bwd_weight_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, workspace, dw, n,
-                     (int)nrc, accumulate);
-  return launch_status("dwconv3x3_bwd_fused_se reduce");
+  return dw_bwd_fused("dwconv3x3_bwd_fused_se", "dwconv3x3_bwd_fused_se reduce", defer_mark, dy, w, dx, x, dw,
+                      accumulate, N, H, W, C, dw_bn_stats(part, bx, mean, invstd, gamma, beta, act), workspace, &e,
+                      as_stream(stream));
 }
 
 // weight-gradient plan: row kernel (bf16, C/8 <= 256) with `slabs` blocks, or the
 // generic pixel-slab kernel; the workspace holds one [C][9] f32 slab per block
 static void wgrad_plan(const DwShape &s, int dtype, bool *row, int *R, int64_t *slabs) {
   const int C8 = s.C / 8;
-  *row = dtype == EWVIT_BF16 && C8 <= 256 && (s.stride == 1 || s.stride == 2) &&
-         dw_bufok((int64_t)s.N * s.H * s.W * s.C) && dw_bufok((int64_t)s.N * s.Ho * s.Wo * s.C);
+  *row = dtype == EWVIT_BF16 && C8 <= 256 && (s.stride == 1 || s.stride == 2) && dw_buf_fits(s);
   if (*row) {
     *R = 512 / C8;
     const int64_t nrows = (int64_t)s.N * s.Ho;
@@ -1183,26 +1189,19 @@ extern "C" int ewvit_dwconv3x3_bwd_weight(const void *x, const void *dy, float *
   bool row; int R; int64_t nslab;
   wgrad_plan(s, dtype, &row, &R, &nslab);
   const int slabs = (int)nslab;
-  const int64_t npix = (int64_t)s.N * s.Ho * s.Wo;
   hipStream_t st = as_stream(stream);
   if (row) {
     const size_t lds = (size_t)(s.C / 8) * 72 * sizeof(float);
-    if (s.stride == 1)
-      hipLaunchKernelGGL(dw_wgrad_row_bf16_kernel<1>, dim3((unsigned)slabs), dim3(512), lds, st,
-                         (const bf16_t *)x, (const bf16_t *)dy, workspace, s, R);
-    else
-      hipLaunchKernelGGL(dw_wgrad_row_bf16_kernel<2>, dim3((unsigned)slabs), dim3(512), lds, st,
-                         (const bf16_t *)x, (const bf16_t *)dy, workspace, s, R);
+    auto kern = s.stride == 1 ? dw_wgrad_row_bf16_kernel<1> : dw_wgrad_row_bf16_kernel<2>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)slabs), dim3(512), lds, st, (const bf16_t *)x, (const bf16_t *)dy,
+                       workspace, s, R);
   } else {
+    const int64_t npix = (int64_t)s.N * s.Ho * s.Wo;
     dim3 grid((unsigned)slabs, (unsigned)((s.C + 63) / 64));
-    if (dtype == EWVIT_BF16)
-      hipLaunchKernelGGL(dw_bwd_weight_partial_kernel<EWVIT_BF16>, grid, dim3(256), 0, st, x, dy, workspace, s, npix);
-    else
-      hipLaunchKernelGGL(dw_bwd_weight_partial_kernel<EWVIT_F32>, grid, dim3(256), 0, st, x, dy, workspace, s, npix);
+    by_dtype(dtype, [&](auto dt) {
+      hipLaunchKernelGGL(dw_bwd_weight_partial_kernel<dt()>, grid, dim3(256), 0, st, x, dy, workspace, s, npix);
+    });
   }
   if (int rc = launch_status("dwconv3x3_bwd_weight")) return rc;
-  const int64_t n = (int64_t)s.C * 9;
-  hipLaunchKernelGGL(dw_bwd_weight_reduce_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, st, workspace,
-                     dw, n, slabs, accumulate);
-  return launch_status("dwconv3x3_bwd_weight reduce");
+  return dw_wgrad_finish("dwconv3x3_bwd_weight reduce", workspace, dw, (int64_t)s.C * 9, slabs, accumulate, false, st);
 }

@@ -124,12 +124,10 @@ extern "C" int ewvit_maxpool2_fwd(const void *x, void *y, uint8_t *argmax, int d
                   (long long)W, (long long)C);
   const int64_t nvec = N * (H / 2) * (W / 2) * (C / 8);
   const dim3 grid((unsigned)((nvec + 255) / 256));
-  if (dtype == EWVIT_BF16)
-    hipLaunchKernelGGL(maxpool2_fwd_kernel<EWVIT_BF16>, grid, dim3(256), 0, as_stream(stream), x, y, argmax, (int)H,
-                       (int)W, (int)C, nvec);
-  else
-    hipLaunchKernelGGL(maxpool2_fwd_kernel<EWVIT_F32>, grid, dim3(256), 0, as_stream(stream), x, y, argmax, (int)H,
-                       (int)W, (int)C, nvec);
+  by_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(maxpool2_fwd_kernel<dt()>, grid, dim3(256), 0, as_stream(stream), x, y, argmax, (int)H, (int)W,
+                       (int)C, nvec);
+  });
   return launch_status("maxpool2_fwd");
 }
 
@@ -141,11 +139,9 @@ extern "C" int ewvit_maxpool2_bwd(const void *dy, const uint8_t *argmax, void *d
                   (long long)W, (long long)C);
   const int64_t nvec = N * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8);
   const dim3 grid((unsigned)((nvec + 255) / 256));
-  if (dtype == EWVIT_BF16)
-    hipLaunchKernelGGL(maxpool2_bwd_kernel<EWVIT_BF16>, grid, dim3(256), 0, as_stream(stream), dy, argmax, dx,
-                       (int)H, (int)W, (int)C, nvec);
-  else
-    hipLaunchKernelGGL(maxpool2_bwd_kernel<EWVIT_F32>, grid, dim3(256), 0, as_stream(stream), dy, argmax, dx,
-                       (int)H, (int)W, (int)C, nvec);
+  by_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(maxpool2_bwd_kernel<dt()>, grid, dim3(256), 0, as_stream(stream), dy, argmax, dx, (int)H, (int)W,
+                       (int)C, nvec);
+  });
   return launch_status("maxpool2_bwd");
 }

@@ -17,36 +17,6 @@
 
 namespace ewvit {
 
-template <int DT>
-__device__ __forceinline__ void se_ld8(const void *p, int64_t i, float (&v)[8]) {
-  if constexpr (DT == EWVIT_BF16) {
-    const uint4 q = *reinterpret_cast<const uint4 *>(reinterpret_cast<const bf16_t *>(p) + i);
-    const unsigned w[4] = {q.x, q.y, q.z, q.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[2 * j] = __uint_as_float(w[j] << 16);
-      v[2 * j + 1] = __uint_as_float(w[j] & 0xffff0000u);
-    }
-  } else {
-    const float4 *q = reinterpret_cast<const float4 *>(reinterpret_cast<const float *>(p) + i);
-    const float4 a = q[0], b = q[1];
-    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  }
-}
-template <int DT>
-__device__ __forceinline__ void se_st8(void *p, int64_t i, const float (&v)[8]) {
-  if constexpr (DT == EWVIT_BF16) {
-    unsigned w[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = (unsigned)f2bf(v[2 * j]) | ((unsigned)f2bf(v[2 * j + 1]) << 16);
-    *reinterpret_cast<uint4 *>(reinterpret_cast<bf16_t *>(p) + i) = make_uint4(w[0], w[1], w[2], w[3]);
-  } else {
-    float4 *q = reinterpret_cast<float4 *>(reinterpret_cast<float *>(p) + i);
-    q[0] = make_float4(v[0], v[1], v[2], v[3]);
-    q[1] = make_float4(v[4], v[5], v[6], v[7]);
-  }
-}
-
 struct SePlan {
   int C8, LC, R, cblocks, S;
   int rows_per_split;
@@ -99,8 +69,8 @@ __global__ __launch_bounds__(256) void se_reduce_kernel(const void *__restrict__
       float va[8][8], vb[8][8];
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
-        se_ld8<DT>(a, base + (int64_t)(h + q * R) * C, va[q]);
-        if (PROD) se_ld8<DT>(b, base + (int64_t)(h + q * R) * C, vb[q]);
+        ld8<DT>(a, base + (int64_t)(h + q * R) * C, va[q]);
+        if (PROD) ld8<DT>(b, base + (int64_t)(h + q * R) * C, vb[q]);
       }
 #pragma unroll
       for (int q = 0; q < 8; ++q)
@@ -109,8 +79,8 @@ __global__ __launch_bounds__(256) void se_reduce_kernel(const void *__restrict__
     }
     for (; h < h1; h += R) {
       float va[8], vb[8];
-      se_ld8<DT>(a, base + (int64_t)h * C, va);
-      if (PROD) se_ld8<DT>(b, base + (int64_t)h * C, vb);
+      ld8<DT>(a, base + (int64_t)h * C, va);
+      if (PROD) ld8<DT>(b, base + (int64_t)h * C, vb);
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[j] = PROD ? fmaf(va[j], vb[j], acc[j]) : acc[j] + va[j];
     }
@@ -165,10 +135,10 @@ __global__ __launch_bounds__(256) void se_scale_kernel(const void *__restrict__ 
     gv[0] = g0.x; gv[1] = g0.y; gv[2] = g0.z; gv[3] = g0.w; gv[4] = g1.x; gv[5] = g1.y; gv[6] = g1.z; gv[7] = g1.w;
   }
   float vx[8];
-  se_ld8<DT>(x, v * 8, vx);
+  ld8<DT>(x, v * 8, vx);
 #pragma unroll
   for (int j = 0; j < 8; ++j) vx[j] = fmaf(vx[j], sc[j], gv[j]);
-  se_st8<DT>(y, v * 8, vx);
+  st8<DT>(y, v * 8, vx);
 }
 
 // y = r * scale[n] (+ x): StochasticDepth(mode='row') times its keep/(1-p) factor,
@@ -181,11 +151,11 @@ __global__ __launch_bounds__(256) void scale_add_kernel(const void *__restrict__
   if (v >= nvec) return;
   const float sc = scale[v / row_vec];
   float vr[8], vx[8];
-  se_ld8<DT>(r, v * 8, vr);
-  if (x) se_ld8<DT>(x, v * 8, vx);
+  ld8<DT>(r, v * 8, vr);
+  if (x) ld8<DT>(x, v * 8, vx);
 #pragma unroll
   for (int j = 0; j < 8; ++j) vr[j] = x ? fmaf(vr[j], sc, vx[j]) : vr[j] * sc;
-  se_st8<DT>(y, v * 8, vr);
+  st8<DT>(y, v * 8, vr);
 }
 
 // StochasticDepth(row) drawn in-kernel: scale[n] = (u(n) < keep) / keep with u the
@@ -203,11 +173,11 @@ __global__ __launch_bounds__(256) void scale_add_drop_kernel(const void *__restr
   const float sc = uniform01(step_seed(seed, seed_offset), (uint64_t)n) < keep ? 1.f / keep : 0.f;
   if (v == n * row_vec) scale_out[n] = sc;
   float vr[8], vx[8];
-  se_ld8<DT>(r, v * 8, vr);
-  se_ld8<DT>(x, v * 8, vx);
+  ld8<DT>(r, v * 8, vr);
+  ld8<DT>(x, v * 8, vx);
 #pragma unroll
   for (int j = 0; j < 8; ++j) vr[j] = fmaf(vr[j], sc, vx[j]);
-  se_st8<DT>(y, v * 8, vr);
+  st8<DT>(y, v * 8, vr);
 }
 
 // ---------------------------------------------------------------- squeeze MLP
@@ -335,7 +305,7 @@ __global__ __launch_bounds__(256) void se_gate_scale_kernel(const float *__restr
 #pragma unroll
   for (int q = 0; q < PF; ++q) {
     const int r = rg + RS * q;
-    if (active && r < HW) se_ld8<DT>(x, base + (int64_t)r * C, pre[q]);
+    if (active && r < HW) ld8<DT>(x, base + (int64_t)r * C, pre[q]);
   }
   const float *pp = part + (int64_t)n * nb * Csq;
   for (int j = tid; j < Csq; j += 256) {
@@ -362,20 +332,20 @@ __global__ __launch_bounds__(256) void se_gate_scale_kernel(const float *__restr
     if (r < HW) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) pre[q][j] = fmaf(pre[q][j], sc[j], 0.f);
-      se_st8<DT>(y, base + (int64_t)r * C, pre[q]);
+      st8<DT>(y, base + (int64_t)r * C, pre[q]);
     }
   }
   for (int r0 = rg + RS * PF; r0 < HW; r0 += RS * PF) {
     float v[PF][8];
 #pragma unroll
     for (int q = 0; q < PF; ++q)
-      if (r0 + RS * q < HW) se_ld8<DT>(x, base + (int64_t)(r0 + RS * q) * C, v[q]);
+      if (r0 + RS * q < HW) ld8<DT>(x, base + (int64_t)(r0 + RS * q) * C, v[q]);
 #pragma unroll
     for (int q = 0; q < PF; ++q) {
       if (r0 + RS * q < HW) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[q][j] = fmaf(v[q][j], sc[j], 0.f);
-        se_st8<DT>(y, base + (int64_t)(r0 + RS * q) * C, v[q]);
+        st8<DT>(y, base + (int64_t)(r0 + RS * q) * C, v[q]);
       }
     }
   }
@@ -584,8 +554,8 @@ __device__ __forceinline__ float se_chunk_squeeze(const void *__restrict__ a, co
       float va[4][8], vb[4][8];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        se_ld8<DT>(a, base + (int64_t)(h + 32 * q) * C, va[q]);
-        if (PROD) se_ld8<DT>(b, base + (int64_t)(h + 32 * q) * C, vb[q]);
+        ld8<DT>(a, base + (int64_t)(h + 32 * q) * C, va[q]);
+        if (PROD) ld8<DT>(b, base + (int64_t)(h + 32 * q) * C, vb[q]);
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q)
@@ -594,8 +564,8 @@ __device__ __forceinline__ float se_chunk_squeeze(const void *__restrict__ a, co
     }
     for (; h < HW; h += 32) {
       float va[8], vb[8];
-      se_ld8<DT>(a, base + (int64_t)h * C, va);
-      if (PROD) se_ld8<DT>(b, base + (int64_t)h * C, vb);
+      ld8<DT>(a, base + (int64_t)h * C, va);
+      if (PROD) ld8<DT>(b, base + (int64_t)h * C, vb);
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[j] = PROD ? fmaf(va[j], vb[j], acc[j]) : acc[j] + va[j];
     }
@@ -702,14 +672,7 @@ __global__ __launch_bounds__(256) void se_sq_dh_part_kernel(const void *__restri
 // streams dy and a anyway; se_mlp_wgrad_kernel, which already sums over the frames, adds the
 // two channel sums; the BN's own reduction pass over dy and z never runs.
 template <int ACT>
-__device__ __forceinline__ float se_act_grad(float z) {   // = batchnorm.hip act_grad
-  if (ACT == 1) return z > 0.f ? 1.f : 0.f;
-  if (ACT == 2) {
-    const float s = __builtin_amdgcn_rcpf(1.f + __expf(-z));
-    return s * (1.f + z * (1.f - s));
-  }
-  return 1.f;
-}
+__device__ __forceinline__ float se_act_grad(float z) { return bn_act_grad(ACT, z); }
 
 template <int V> struct se_ic { static constexpr int value = V; };
 // raw 8-channel vectors (bf16: one 16-B load, unpacked at use) for the batched row walks
@@ -918,12 +881,14 @@ extern "C" int ewvit_se_reduce(const void *a, const void *b, int dtype, int64_t 
   const SePlan p = se_plan(N, HW, C);
   hipStream_t s = as_stream(stream);
   dim3 grid((unsigned)(N * p.S), (unsigned)p.cblocks);
-#define SE_RED(DTV, PV)                                                                                        \
-  hipLaunchKernelGGL((se_reduce_kernel<DTV, PV>), grid, dim3(256), 0, s, a, b, (int)HW, (int)C, p.R, p.LC, p.S, \
-                     p.rows_per_split, workspace, (int)N, scale, out)
-  if (dtype == EWVIT_BF16) { if (b) SE_RED(EWVIT_BF16, 1); else SE_RED(EWVIT_BF16, 0); }
-  else { if (b) SE_RED(EWVIT_F32, 1); else SE_RED(EWVIT_F32, 0); }
-#undef SE_RED
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(256), 0, s, a, b, (int)HW, (int)C, p.R, p.LC, p.S, p.rows_per_split, workspace,
+                       (int)N, scale, out);
+  };
+  by_dtype(dtype, [&](auto dt) {
+    if (b) go(se_reduce_kernel<dt(), 1>);
+    else go(se_reduce_kernel<dt(), 0>);
+  });
   if (p.S > 1) {
     const int64_t NC = N * C;
     hipLaunchKernelGGL(se_fold_kernel, dim3((unsigned)((NC + 255) / 256)), dim3(256), 0, s, workspace, p.S, NC,
@@ -938,12 +903,9 @@ extern "C" int ewvit_se_scale(const void *x, int dtype, const float *s, const fl
   EWVIT_CHECK_ARG(x && s && y, "se_scale: null pointer");
   const int64_t nvec = N * HW * C / 8;
   dim3 grid((unsigned)((nvec + 255) / 256));
-  if (dtype == EWVIT_BF16)
-    hipLaunchKernelGGL(se_scale_kernel<EWVIT_BF16>, grid, dim3(256), 0, as_stream(stream), x, s, g, y, nvec,
-                       (int)HW, (int)C);
-  else
-    hipLaunchKernelGGL(se_scale_kernel<EWVIT_F32>, grid, dim3(256), 0, as_stream(stream), x, s, g, y, nvec,
-                       (int)HW, (int)C);
+  by_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(se_scale_kernel<dt()>, grid, dim3(256), 0, as_stream(stream), x, s, g, y, nvec, (int)HW, (int)C);
+  });
   return launch_status("se_scale");
 }
 
@@ -954,12 +916,10 @@ extern "C" int ewvit_scale_add(const void *r, const void *x, int dtype, const fl
                   "scale_add: bad args (row_elems %% 8 == 0)");
   const int64_t nvec = N * row_elems / 8;
   dim3 grid((unsigned)((nvec + 255) / 256));
-  if (dtype == EWVIT_BF16)
-    hipLaunchKernelGGL(scale_add_kernel<EWVIT_BF16>, grid, dim3(256), 0, as_stream(stream), r, x, scale, y, nvec,
+  by_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(scale_add_kernel<dt()>, grid, dim3(256), 0, as_stream(stream), r, x, scale, y, nvec,
                        row_elems / 8);
-  else
-    hipLaunchKernelGGL(scale_add_kernel<EWVIT_F32>, grid, dim3(256), 0, as_stream(stream), r, x, scale, y, nvec,
-                       row_elems / 8);
+  });
   return launch_status("scale_add");
 }
 
@@ -972,25 +932,83 @@ extern "C" int ewvit_scale_add_drop(const void *r, const void *x, int dtype, flo
   EWVIT_CHECK_ARG(keep_prob > 0.f && keep_prob <= 1.f, "scale_add_drop: keep_prob %g", (double)keep_prob);
   const int64_t nvec = N * row_elems / 8;
   dim3 grid((unsigned)((nvec + 255) / 256));
-  if (dtype == EWVIT_BF16)
-    hipLaunchKernelGGL(scale_add_drop_kernel<EWVIT_BF16>, grid, dim3(256), 0, as_stream(stream), r, x, keep_prob,
-                       seed, seed_offset, scale_out, y, nvec, row_elems / 8);
-  else
-    hipLaunchKernelGGL(scale_add_drop_kernel<EWVIT_F32>, grid, dim3(256), 0, as_stream(stream), r, x, keep_prob,
-                       seed, seed_offset, scale_out, y, nvec, row_elems / 8);
+  by_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(scale_add_drop_kernel<dt()>, grid, dim3(256), 0, as_stream(stream), r, x, keep_prob, seed,
+                       seed_offset, scale_out, y, nvec, row_elems / 8);
+  });
   return launch_status("scale_add_drop");
 }
 
+// ---- the squeeze MLP: checks, shape and the launches its entry points share
 static int se_mlp_check(int64_t N, int64_t C, int64_t Csq, const char *nm) {
   EWVIT_CHECK_ARG(N > 0 && C > 0 && Csq > 0 && C <= 65535 * 64 && Csq <= 8192, "%s: N=%lld C=%lld Csq=%lld", nm,
                   (long long)N, (long long)C, (long long)Csq);
   return 0;
 }
+static int se_check(int dtype, int64_t N, int64_t HW, int64_t C, int64_t Csq, const char *nm) {
+  if (int rc = se_check(dtype, N, HW, C, nm)) return rc;
+  return se_mlp_check(N, C, Csq, nm);
+}
 
-static int se_nb(int64_t C) { return (int)((C + SE_CB - 1) / SE_CB); }
+struct SeShape {
+  int64_t N, HW, C, Csq;
+  int nb() const { return (int)((C + SE_CB - 1) / SE_CB); }       // 64-channel chunks
+  dim3 grid() const { return dim3((unsigned)N, (unsigned)nb()); }  // one block per (frame, chunk)
+  float inv_hw() const { return 1.f / (float)HW; }
+};
+
+// squeeze s0 = mean_hw x and the first layer's per-chunk partials part [N][nb][Csq]
+static void se_launch_squeeze_h1(const SeShape &e, const void *x, int dtype, const float *w1, float *s0, float *part,
+                                 hipStream_t st) {
+  by_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(se_sq_h1_part_kernel<dt()>, e.grid(), dim3(256), 0, st, x, (int)e.HW, e.inv_hw(), w1, (int)e.C,
+                       (int)e.Csq, s0, part);
+  });
+}
+
+// the gates h1, s from the partials
+static void se_launch_gate(const SeShape &e, const float *part, const float *b1, const float *w2, const float *b2,
+                           float *h1, float *s, hipStream_t st) {
+  hipLaunchKernelGGL(se_mlp_gate_kernel, e.grid(), dim3(256), (size_t)e.Csq * sizeof(float), st, part, e.nb(), b1, w2,
+                     b2, (int)e.C, (int)e.Csq, h1, s);
+}
+
+// the gates and the excite pass y = x * s in one launch
+static void se_launch_gate_excite(const SeShape &e, const float *part, const float *b1, const float *w2,
+                                  const float *b2, float *h1, float *s, const void *x, void *y, int dtype,
+                                  hipStream_t st) {
+  const size_t lds = (size_t)(((e.Csq + 3) & ~3) + 256) * sizeof(float);
+  by_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(se_gate_scale_kernel<dt()>, e.grid(), dim3(256), lds, st, part, e.nb(), b1, w2, b2, (int)e.C,
+                       (int)e.Csq, h1, s, x, y, (int)e.HW);
+  });
+}
+
+// the backward's workspace (float offsets): dz2 [N][C] | dz1 [N][Csq] | part [N][nb][Csq], and
+// for ewvit_bn_se_bwd the BatchNorm's per-frame sums bnsum [4][N][C] | its sums row bnrow [2C]
+struct SeBwdWs { int64_t dz2, dz1, part, bnsum, bnrow, end; };   // bnsum: where the MLP backward's own part ends
+static SeBwdWs se_bwd_ws(const SeShape &e) {
+  const int64_t dz1 = e.N * e.C, part = dz1 + e.N * e.Csq, bnsum = part + e.N * e.nb() * e.Csq;
+  return {0, dz1, part, bnsum, bnsum + 4 * e.N * e.C, bnsum + 4 * e.N * e.C + 2 * e.C};
+}
+
+// the backward's tail from dz2 and the partials: g + dz1, then the weight gradients; bn_s given
+// (the excitation, ewvit_bn_se_bwd): extra blocks fold bnsum into bnrow and dbeta / dgamma
+static void se_launch_bwd_tail(const SeShape &e, float *ws, const float *h1, const float *s0, const float *w1,
+                               float inv_hw, float *g, float *dw1, float *db1, float *dw2, float *db2,
+                               const float *bn_s, float *bn_dbeta, float *bn_dgamma, hipStream_t st) {
+  const SeBwdWs o = se_bwd_ws(e);
+  hipLaunchKernelGGL(se_mlp_g_kernel, e.grid(), dim3(256), (size_t)e.Csq * sizeof(float), st, ws + o.part, e.nb(), h1,
+                     w1, (int)e.C, (int)e.Csq, inv_hw, ws + o.dz1, g);
+  const int64_t tot = 2 * e.C * e.Csq + e.C + e.Csq;
+  const int nwb = (int)((tot + 63) / 64), nbn = bn_s ? (int)((2 * e.C + 63) / 64) : 0;
+  hipLaunchKernelGGL(se_mlp_wgrad_kernel, dim3((unsigned)(nwb + nbn)), dim3(256), 0, st, ws + o.dz2, ws + o.dz1, h1, s0,
+                     (int)e.N, (int)e.C, (int)e.Csq, dw1, db1, dw2, db2, bn_s ? ws + o.bnsum : nullptr, bn_s,
+                     bn_s ? g : nullptr, bn_s ? ws + o.bnrow : nullptr, bn_s ? nwb : 0, bn_dbeta, bn_dgamma);
+}
 
 extern "C" int64_t ewvit_se_mlp_fwd_workspace(int64_t N, int64_t C, int64_t Csq) {
-  return N * se_nb(C) * Csq * (int64_t)sizeof(float);
+  return N * SeShape{N, 1, C, Csq}.nb() * Csq * (int64_t)sizeof(float);
 }
 
 extern "C" int ewvit_se_mlp_fwd(const float *s0, const float *w1, const float *b1, const float *w2, const float *b2,
@@ -999,16 +1017,14 @@ extern "C" int ewvit_se_mlp_fwd(const float *s0, const float *w1, const float *b
   if (int rc = se_mlp_check(N, C, Csq, "se_mlp_fwd")) return rc;
   EWVIT_CHECK_ARG(s0 && w1 && w2 && h1 && s && workspace, "se_mlp_fwd: null pointer");
   hipStream_t st = as_stream(stream);
-  const int nb = se_nb(C);
-  hipLaunchKernelGGL(se_mlp_h1_part_kernel, dim3((unsigned)N, (unsigned)nb), dim3(256), 0, st, s0, w1, (int)C,
-                     (int)Csq, workspace);
-  hipLaunchKernelGGL(se_mlp_gate_kernel, dim3((unsigned)N, (unsigned)((C + 63) / 64)), dim3(256),
-                     (size_t)Csq * sizeof(float), st, workspace, nb, b1, w2, b2, (int)C, (int)Csq, h1, s);
+  const SeShape e{N, 1, C, Csq};
+  hipLaunchKernelGGL(se_mlp_h1_part_kernel, e.grid(), dim3(256), 0, st, s0, w1, (int)C, (int)Csq, workspace);
+  se_launch_gate(e, workspace, b1, w2, b2, h1, s, st);
   return launch_status("se_mlp_fwd");
 }
 
 extern "C" int64_t ewvit_se_mlp_bwd_workspace(int64_t N, int64_t C, int64_t Csq) {
-  return N * (C + Csq + se_nb(C) * Csq) * (int64_t)sizeof(float);
+  return se_bwd_ws({N, 1, C, Csq}).bnsum * (int64_t)sizeof(float);
 }
 
 extern "C" int ewvit_se_mlp_bwd(const float *ds, const float *s, const float *h1, const float *s0, const float *w1,
@@ -1017,15 +1033,11 @@ extern "C" int ewvit_se_mlp_bwd(const float *ds, const float *s, const float *h1
   if (int rc = se_mlp_check(N, C, Csq, "se_mlp_bwd")) return rc;
   EWVIT_CHECK_ARG(ds && s && h1 && s0 && w1 && w2 && g && dw1 && dw2 && workspace, "se_mlp_bwd: null pointer");
   hipStream_t st = as_stream(stream);
-  const int nb = se_nb(C);
-  float *dz2 = workspace, *dz1 = workspace + N * C, *part = dz1 + N * Csq;
-  hipLaunchKernelGGL(se_mlp_dh_part_kernel, dim3((unsigned)N, (unsigned)nb), dim3(256), 0, st, ds, s, w2, (int)C,
-                     (int)Csq, dz2, part);
-  hipLaunchKernelGGL(se_mlp_g_kernel, dim3((unsigned)N, (unsigned)((C + 63) / 64)), dim3(256),
-                     (size_t)Csq * sizeof(float), st, part, nb, h1, w1, (int)C, (int)Csq, inv_hw, dz1, g);
-  const int64_t tot = 2 * C * Csq + C + Csq;
-  hipLaunchKernelGGL(se_mlp_wgrad_kernel, dim3((unsigned)((tot + 63) / 64)), dim3(256), 0, st, dz2, dz1, h1, s0,
-                     (int)N, (int)C, (int)Csq, dw1, db1, dw2, db2);
+  const SeShape e{N, 1, C, Csq};
+  const SeBwdWs o = se_bwd_ws(e);
+  hipLaunchKernelGGL(se_mlp_dh_part_kernel, e.grid(), dim3(256), 0, st, ds, s, w2, (int)C, (int)Csq,
+                     workspace + o.dz2, workspace + o.part);
+  se_launch_bwd_tail(e, workspace, h1, s0, w1, inv_hw, g, dw1, db1, dw2, db2, nullptr, nullptr, nullptr, st);
   return launch_status("se_mlp_bwd");
 }
 
@@ -1034,20 +1046,12 @@ extern "C" int ewvit_se_mlp_bwd(const float *ds, const float *s, const float *h1
 extern "C" int ewvit_se_squeeze_mlp_fwd(const void *x, int dtype, int64_t N, int64_t HW, int64_t C, const float *w1,
                                         const float *b1, const float *w2, const float *b2, int64_t Csq, float *s0,
                                         float *h1, float *s, float *workspace, void *stream) {
-  if (int rc = se_check(dtype, N, HW, C, "se_squeeze_mlp_fwd")) return rc;
-  if (int rc = se_mlp_check(N, C, Csq, "se_squeeze_mlp_fwd")) return rc;
+  if (int rc = se_check(dtype, N, HW, C, Csq, "se_squeeze_mlp_fwd")) return rc;
   EWVIT_CHECK_ARG(x && w1 && w2 && s0 && h1 && s && workspace && HW < (1 << 30), "se_squeeze_mlp_fwd: bad args");
   hipStream_t st = as_stream(stream);
-  const int nb = se_nb(C);
-  const dim3 g1((unsigned)N, (unsigned)nb);
-  if (dtype == EWVIT_BF16)
-    hipLaunchKernelGGL(se_sq_h1_part_kernel<EWVIT_BF16>, g1, dim3(256), 0, st, x, (int)HW, 1.f / (float)HW, w1,
-                       (int)C, (int)Csq, s0, workspace);
-  else
-    hipLaunchKernelGGL(se_sq_h1_part_kernel<EWVIT_F32>, g1, dim3(256), 0, st, x, (int)HW, 1.f / (float)HW, w1,
-                       (int)C, (int)Csq, s0, workspace);
-  hipLaunchKernelGGL(se_mlp_gate_kernel, dim3((unsigned)N, (unsigned)((C + 63) / 64)), dim3(256),
-                     (size_t)Csq * sizeof(float), st, workspace, nb, b1, w2, b2, (int)C, (int)Csq, h1, s);
+  const SeShape e{N, HW, C, Csq};
+  se_launch_squeeze_h1(e, x, dtype, w1, s0, workspace, st);
+  se_launch_gate(e, workspace, b1, w2, b2, h1, s, st);
   return launch_status("se_squeeze_mlp_fwd");
 }
 
@@ -1056,25 +1060,12 @@ extern "C" int ewvit_se_squeeze_mlp_fwd(const void *x, int dtype, int64_t N, int
 extern "C" int ewvit_se_forward(const void *x, int dtype, int64_t N, int64_t HW, int64_t C, const float *w1,
                                 const float *b1, const float *w2, const float *b2, int64_t Csq, float *s0, float *h1,
                                 float *s, void *y, float *workspace, void *stream) {
-  if (int rc = se_check(dtype, N, HW, C, "se_forward")) return rc;
-  if (int rc = se_mlp_check(N, C, Csq, "se_forward")) return rc;
+  if (int rc = se_check(dtype, N, HW, C, Csq, "se_forward")) return rc;
   EWVIT_CHECK_ARG(x && w1 && w2 && s0 && h1 && s && y && workspace && HW < (1 << 30), "se_forward: bad args");
   hipStream_t st = as_stream(stream);
-  const int nb = se_nb(C);
-  const dim3 g1((unsigned)N, (unsigned)nb);
-  const dim3 g2((unsigned)N, (unsigned)((C + 63) / 64));
-  const size_t lds = (size_t)(((Csq + 3) & ~3) + 256) * sizeof(float);
-  if (dtype == EWVIT_BF16) {
-    hipLaunchKernelGGL(se_sq_h1_part_kernel<EWVIT_BF16>, g1, dim3(256), 0, st, x, (int)HW, 1.f / (float)HW, w1,
-                       (int)C, (int)Csq, s0, workspace);
-    hipLaunchKernelGGL(se_gate_scale_kernel<EWVIT_BF16>, g2, dim3(256), lds, st, workspace, nb, b1, w2, b2, (int)C,
-                       (int)Csq, h1, s, x, y, (int)HW);
-  } else {
-    hipLaunchKernelGGL(se_sq_h1_part_kernel<EWVIT_F32>, g1, dim3(256), 0, st, x, (int)HW, 1.f / (float)HW, w1,
-                       (int)C, (int)Csq, s0, workspace);
-    hipLaunchKernelGGL(se_gate_scale_kernel<EWVIT_F32>, g2, dim3(256), lds, st, workspace, nb, b1, w2, b2, (int)C,
-                       (int)Csq, h1, s, x, y, (int)HW);
-  }
+  const SeShape e{N, HW, C, Csq};
+  se_launch_squeeze_h1(e, x, dtype, w1, s0, workspace, st);
+  se_launch_gate_excite(e, workspace, b1, w2, b2, h1, s, x, y, dtype, st);
   return launch_status("se_forward");
 }
 
@@ -1083,17 +1074,9 @@ extern "C" int ewvit_se_forward(const void *x, int dtype, int64_t N, int64_t HW,
 extern "C" int ewvit_se_gate_excite(const float *part, const float *b1, const float *w2, const float *b2,
                                     const void *x, int dtype, int64_t N, int64_t HW, int64_t C, int64_t Csq, float *h1,
                                     float *s, void *y, void *stream) {
-  if (int rc = se_check(dtype, N, HW, C, "se_gate_excite")) return rc;
-  if (int rc = se_mlp_check(N, C, Csq, "se_gate_excite")) return rc;
+  if (int rc = se_check(dtype, N, HW, C, Csq, "se_gate_excite")) return rc;
   EWVIT_CHECK_ARG(part && w2 && h1 && s && x && y && HW < (1 << 30), "se_gate_excite: bad args");
-  const dim3 g2((unsigned)N, (unsigned)((C + 63) / 64));
-  const size_t lds = (size_t)(((Csq + 3) & ~3) + 256) * sizeof(float);
-  if (dtype == EWVIT_BF16)
-    hipLaunchKernelGGL(se_gate_scale_kernel<EWVIT_BF16>, g2, dim3(256), lds, as_stream(stream), part, se_nb(C), b1, w2,
-                       b2, (int)C, (int)Csq, h1, s, x, y, (int)HW);
-  else
-    hipLaunchKernelGGL(se_gate_scale_kernel<EWVIT_F32>, g2, dim3(256), lds, as_stream(stream), part, se_nb(C), b1, w2,
-                       b2, (int)C, (int)Csq, h1, s, x, y, (int)HW);
+  se_launch_gate_excite({N, HW, C, Csq}, part, b1, w2, b2, h1, s, x, y, dtype, as_stream(stream));
   return launch_status("se_gate_excite");
 }
 
@@ -1101,35 +1084,27 @@ extern "C" int ewvit_se_squeeze_mlp_bwd(const void *dy, const void *x, int dtype
                                         const float *s, const float *h1, const float *s0, const float *w1,
                                         const float *w2, int64_t Csq, float *g, float *dw1, float *db1, float *dw2,
                                         float *db2, float *workspace, void *stream) {
-  if (int rc = se_check(dtype, N, HW, C, "se_squeeze_mlp_bwd")) return rc;
-  if (int rc = se_mlp_check(N, C, Csq, "se_squeeze_mlp_bwd")) return rc;
+  if (int rc = se_check(dtype, N, HW, C, Csq, "se_squeeze_mlp_bwd")) return rc;
   EWVIT_CHECK_ARG(dy && x && s && h1 && s0 && w1 && w2 && g && dw1 && dw2 && workspace && HW < (1 << 30),
                   "se_squeeze_mlp_bwd: bad args");
   hipStream_t st = as_stream(stream);
-  const int nb = se_nb(C);
-  float *dz2 = workspace, *dz1 = workspace + N * C, *part = dz1 + N * Csq;
-  const dim3 g1((unsigned)N, (unsigned)nb);
-  if (dtype == EWVIT_BF16)
-    hipLaunchKernelGGL(se_sq_dh_part_kernel<EWVIT_BF16>, g1, dim3(256), 0, st, dy, x, (int)HW, s, w2, (int)C,
-                       (int)Csq, dz2, part);
-  else
-    hipLaunchKernelGGL(se_sq_dh_part_kernel<EWVIT_F32>, g1, dim3(256), 0, st, dy, x, (int)HW, s, w2, (int)C,
-                       (int)Csq, dz2, part);
-  hipLaunchKernelGGL(se_mlp_g_kernel, dim3((unsigned)N, (unsigned)((C + 63) / 64)), dim3(256),
-                     (size_t)Csq * sizeof(float), st, part, nb, h1, w1, (int)C, (int)Csq, 1.f / (float)HW, dz1, g);
-  const int64_t tot = 2 * C * Csq + C + Csq;
-  hipLaunchKernelGGL(se_mlp_wgrad_kernel, dim3((unsigned)((tot + 63) / 64)), dim3(256), 0, st, dz2, dz1, h1, s0,
-                     (int)N, (int)C, (int)Csq, dw1, db1, dw2, db2);
+  const SeShape e{N, HW, C, Csq};
+  const SeBwdWs o = se_bwd_ws(e);
+  by_dtype(dtype, [&](auto dt) {
+    hipLaunchKernelGGL(se_sq_dh_part_kernel<dt()>, e.grid(), dim3(256), 0, st, dy, x, (int)HW, s, w2, (int)C, (int)Csq,
+                       workspace + o.dz2, workspace + o.part);
+  });
+  se_launch_bwd_tail(e, workspace, h1, s0, w1, e.inv_hw(), g, dw1, db1, dw2, db2, nullptr, nullptr, nullptr, st);
   return launch_status("se_squeeze_mlp_bwd");
 }
 
 extern "C" int64_t ewvit_bn_se_bwd_workspace(int64_t N, int64_t C, int64_t Csq) {
-  return ewvit_se_mlp_bwd_workspace(N, C, Csq) + (4 * N * C + 2 * C) * (int64_t)sizeof(float);
+  return se_bwd_ws({N, 1, C, Csq}).end * (int64_t)sizeof(float);
 }
 
 // where ewvit_bn_se_bwd leaves the BN's sums row [2C] (sum g', sum g' zhat) in its workspace (floats)
 extern "C" int64_t ewvit_bn_se_bwd_row_offset(int64_t N, int64_t C, int64_t Csq) {
-  return ewvit_se_mlp_bwd_workspace(N, C, Csq) / (int64_t)sizeof(float) + 4 * N * C;
+  return se_bwd_ws({N, 1, C, Csq}).bnrow;
 }
 
 // the dx pass alone, from the sums row ewvit_bn_se_bwd (dx NULL) left: dx = the BN input gradient
@@ -1155,8 +1130,7 @@ extern "C" int ewvit_bn_se_bwd(const void *dy, const void *a, const void *z, voi
                                const float *h1, const float *s0, const float *w1, const float *w2, int64_t Csq,
                                float *g, float *dw1, float *db1, float *dw2, float *db2, float *workspace,
                                void *stream) {
-  if (int rc = se_check(dtype, N, HW, C, "bn_se_bwd")) return rc;
-  if (int rc = se_mlp_check(N, C, Csq, "bn_se_bwd")) return rc;
+  if (int rc = se_check(dtype, N, HW, C, Csq, "bn_se_bwd")) return rc;
   // dx NULL: the dx pass is left to the depthwise conv's backward (ewvit_dwconv3x3_bwd_fused_se, which
   // forms dz from dy and z); dgamma / dbeta come from the sums blocks, the sums row stays in the
   // workspace at ewvit_bn_se_bwd_row_offset floats
@@ -1166,32 +1140,17 @@ extern "C" int ewvit_bn_se_bwd(const void *dy, const void *a, const void *z, voi
   EWVIT_CHECK_ARG(act >= 0 && act <= 2 && C <= 4096 && N * HW < ((int64_t)1 << 31), "bn_se_bwd: act=%d C=%lld", act,
                   (long long)C);
   hipStream_t st = as_stream(stream);
-  const int nb = se_nb(C);
-  float *dz2 = workspace, *dz1 = workspace + N * C, *part = dz1 + N * Csq;
-  float *bnsum = part + N * nb * Csq, *bnrow = bnsum + 4 * N * C;
-  const dim3 g1((unsigned)N, (unsigned)nb);
-#define SE_BN_DH(DTV, ACTV)                                                                                          \
-  hipLaunchKernelGGL((se_sq_dh_bn_part_kernel<DTV, ACTV>), g1, dim3(256), 0, st, dy, a, z, (int)HW, s, w2, (int)C,  \
-                     (int)Csq, save_mean, save_invstd, gamma, beta, dz2, part, bnsum, (int)N)
-  if (dtype == EWVIT_BF16) {
-    if (act == 0) SE_BN_DH(EWVIT_BF16, 0);
-    else if (act == 1) SE_BN_DH(EWVIT_BF16, 1);
-    else SE_BN_DH(EWVIT_BF16, 2);
-  } else {
-    if (act == 0) SE_BN_DH(EWVIT_F32, 0);
-    else if (act == 1) SE_BN_DH(EWVIT_F32, 1);
-    else SE_BN_DH(EWVIT_F32, 2);
-  }
-#undef SE_BN_DH
-  hipLaunchKernelGGL(se_mlp_g_kernel, dim3((unsigned)N, (unsigned)((C + 63) / 64)), dim3(256),
-                     (size_t)Csq * sizeof(float), st, part, nb, h1, w1, (int)C, (int)Csq, 1.f / (float)HW, dz1, g);
-  const int64_t tot = 2 * C * Csq + C + Csq;
-  const int nwb = (int)((tot + 63) / 64), nbn = (int)((2 * C + 63) / 64);
-  hipLaunchKernelGGL(se_mlp_wgrad_kernel, dim3((unsigned)(nwb + nbn)), dim3(256), 0, st, dz2, dz1, h1, s0, (int)N,
-                     (int)C, (int)Csq, dw1, db1, dw2, db2, bnsum, s, g, bnrow, nwb, dx ? nullptr : dbeta,
-                     dx ? nullptr : dgamma);
+  const SeShape e{N, HW, C, Csq};
+  const SeBwdWs o = se_bwd_ws(e);
+  by_dtype_act(dtype, act, [&](auto dt, auto ac) {
+    hipLaunchKernelGGL((se_sq_dh_bn_part_kernel<dt(), ac()>), e.grid(), dim3(256), 0, st, dy, a, z, (int)HW, s, w2,
+                       (int)C, (int)Csq, save_mean, save_invstd, gamma, beta, workspace + o.dz2, workspace + o.part,
+                       workspace + o.bnsum, (int)N);
+  });
+  se_launch_bwd_tail(e, workspace, h1, s0, w1, e.inv_hw(), g, dw1, db1, dw2, db2, s, dx ? nullptr : dbeta,
+                     dx ? nullptr : dgamma, st);
   if (int rc = launch_status("bn_se_bwd")) return rc;
   if (!dx) return 0;
   return bn_bwd_dx_se_launch(dy, z, dx, dtype, N * HW, C, gamma, beta, save_mean, save_invstd, act, dgamma, dbeta, s,
-                             g, HW, bnrow, 1, st);
+                             g, HW, workspace + o.bnrow, 1, st);
 }
