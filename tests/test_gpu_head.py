@@ -6,9 +6,9 @@ Both round every GEMM operand to bf16 and accumulate in fp32; they differ in sum
 in where intermediates are rounded (the module path stores q / kv in bf16) and in the dropout
 streams.  Bounds: outputs max |err| <= 1e-2 of scale, cosine >= 0.9999; every parameter and
 input gradient cosine >= 0.999 with its norm within 1 %; BatchNorm running statistics 1e-4.
-Dropout is off for the comparison (its masks come from different counters); a separate test
-checks that training-mode dropout draws fresh masks per step and is exactly reproduced by the
-backward.
+Dropout is off for the comparison (its masks come from different counters); with dropout on,
+tests/test_gpu_head_stages.py checks every stage, forward and backward, against float64 with the
+masks recovered from the workspace.
 """
 import pytest
 import torch
@@ -124,10 +124,11 @@ def test_head_matches_module_path(N, training, monkeypatch):
 
 
 def test_head_dropout_fresh_masks_and_consistent_backward(monkeypatch):
-    """Training dropout in the fused head: two steps (step counter advanced) draw different masks;
-    the backward regenerates the forward's mask (a finite-difference check on one input through
-    the whole head in fp32-class accuracy is out of reach with bf16 operands, so the check is that
-    a zero upstream gradient on the dropped units leaves them without gradient)."""
+    """Training dropout in the fused head: two steps (step counter advanced) give different,
+    finite outputs.  That the masks are fresh per step, follow the site and the global frame, and
+    that the backward and the weight-gradient kernel regenerate exactly the forward's masks is
+    checked in tests/test_gpu_head_stages.py (test_head_backward_stages, test_head_masks,
+    test_head_masks_change_with_the_step_counter), with the masks recovered from the workspace."""
     import ewvit
     from network.dama import DAMA
     torch.manual_seed(1)
