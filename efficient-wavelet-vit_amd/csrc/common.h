@@ -250,6 +250,12 @@ inline void by_dtype(int dtype, F &&f) {
   if (dtype == EWVIT_BF16) f(std::integral_constant<int, EWVIT_BF16>{});
   else f(std::integral_constant<int, EWVIT_F32>{});
 }
+// a run-time flag (the ViT layer's MX form) as std::true_type / std::false_type
+template <typename F>
+inline void by_bool(bool b, F &&f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
 template <typename F>
 inline void by_act(int act, F &&f) {
   if (act == 0) f(std::integral_constant<int, 0>{});

@@ -34,10 +34,13 @@
 // gradients stored transposed ([feature][128 rows] bf16, zero past R), written by the kernel
 // that produces them (the MFMA output layout gives a lane 4 consecutive rows of one column).
 // Forward / input-gradient GEMMs read their A fragments straight from global memory (L2) and
-// their B fragments from the fp32 weights (forward) or from an LDS image of the weight slice
-// transposed to k-contiguous bf16 (input gradients reduce over the weight's output index).
-#include "common.h"
-#include "mx8.h"
+// their B fragments from the step's packed weight image (ewvit_vit_pack: bf16, or MXFP8 with
+// p.mx), W for the forward and W^T, k-contiguous, for the input gradients.
+// Each GEMM shape is written once for both operand forms: tile64x32 (F1 / F3 / B1; F2 keeps a copy),
+// dgrad_block (B2 / B4), wgrad_block (B2 / B4) and B3's own slice map; a kernel states its A
+// operand once, as a lambda yielding 8 fp32 values at (row tile, k), which the bf16 form packs and
+// the MX form block-quantizes (frag.h: fragment types, loads, mx_fill).
+#include "frag.h"
 
 namespace ewvit {
 
@@ -47,60 +50,56 @@ constexpr int VF4_SPLIT = 16;      // K splits of Linear2 (ewvit_gemm, K = 2048:
 
 typedef ewvit_vit_layer VitP;
 typedef ewvit_vit_grads VitG;
-typedef __attribute__((ext_vector_type(8))) __bf16 vb8;
-typedef __attribute__((ext_vector_type(4))) float vf4;
 
-__device__ __forceinline__ vf4 mma(vb8 a, vb8 b, vf4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ vb8 pack8(const float *v) {
-  vb8 r;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) r[e] = (__bf16)v[e];
-  return r;
-}
-__device__ __forceinline__ void ld8f(const float *p, float *v) {
-  const float4 a = *reinterpret_cast<const float4 *>(p), b = *reinterpret_cast<const float4 *>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-__device__ __forceinline__ vb8 ld8b(const bf16_t *p) { return *reinterpret_cast<const vb8 *>(p); }
-__device__ __forceinline__ void unpack8(vb8 b, float *v) {
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = (float)b[e];
-}
-__device__ __forceinline__ vb8 zero8() {
-  vb8 r;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) r[e] = (__bf16)0.f;
-  return r;
-}
-__device__ __forceinline__ float rbf(float v) { return bf2f(f2bf(v)); }
-// rows >= R are loaded from row R - 1 (in bounds) and masked after the load: a load under a
-// per-lane branch gets its own block and waits, so the epilogues' loads would run one by one
-__device__ __forceinline__ int rclamp(int r, int R) { return r < R ? r : R - 1; }
 __device__ __forceinline__ float keep_scale(float p, uint64_t sd, uint64_t idx) {
   return uniform01(sd, idx) >= p ? 1.0f / (1.0f - p) : 0.f;
 }
 
 // ---------------------------------------------------------------- saved state / scratch
+__host__ __device__ inline int64_t al256(int64_t b) { return (b + 255) / 256 * 256; }
+// A workspace's buffers, each stated once as put(member, elements): they lie in this order, each
+// rounded up to 256 bytes (the element size is the member's)
 struct VitSaved {
   float *mu1, *rs1, *mu2, *rs2, *p, *x1;
   bf16_t *qkv, *aux, *h, *ln1T, *oT, *ln2T, *hT;
   float *ws2;                       // Linear2's split-K slabs (forward only)
+  template <class F> void fields(F put) {
+    put(mu1, VRP); put(rs1, VRP); put(mu2, VRP); put(rs2, VRP);
+    put(p, VRP * VH * 2); put(x1, VRP * VD);
+    put(qkv, VRP * VQ); put(aux, VRP * VF); put(h, VRP * VF);
+    put(ln1T, VD * VRP); put(oT, VD * VRP); put(ln2T, VD * VRP); put(hT, VF * VRP);
+    put(ws2, VF4_SPLIT * VRP * VD);
+  }
 };
 struct VitScratch {
   bf16_t *gT, *g1, *g1T, *goT, *dqkv, *dqkvT;
   float *dln2, *dx1, *dln1;
   float *rp2, *rp1;                 // LN backward row partials [32 column blocks][128 rows][2]
   float *db1p;                      // Linear1 bias gradient per row half [2][2048]
+  template <class F> void fields(F put) {
+    put(gT, VD * VRP); put(g1, VRP * VF); put(g1T, VF * VRP); put(goT, VD * VRP);
+    put(dqkv, VRP * VQ); put(dqkvT, VQ * VRP);
+    put(dln2, VRP * VD); put(dx1, VRP * VD); put(dln1, VRP * VD);
+    put(rp2, 32 * VRP * 2); put(rp1, 32 * VRP * 2); put(db1p, 2 * VF);
+  }
 };
+// the pointers of workspace S at base; *bytes: its size (what ewvit_vit_layer_workspace reports)
+template <class S> inline S vit_carve(void *base, int64_t *bytes = nullptr) {
+  S s;
+  int64_t o = 0;
+  s.fields([&](auto *&ptr, int64_t n) {
+    ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(reinterpret_cast<char *>(base) + o);
+    o += al256(n * (int64_t)sizeof(*ptr));
+  });
+  if (bytes) *bytes = o;
+  return s;
+}
 // The layer's four weights in bf16, packed once per step by ewvit_vit_pack (fp32 masters read
 // once): each as W [out][in] (forward B fragments, k = in contiguous) and W^T [in][out] (input
 // gradient B fragments, k = out contiguous).  Element offsets within a layer's block:
 constexpr int64_t PK_QKV = 0, PK_QKVT = PK_QKV + (int64_t)VQ * VD, PK_O = PK_QKVT + (int64_t)VQ * VD,
                   PK_OT = PK_O + (int64_t)VD * VD, PK_1 = PK_OT + (int64_t)VD * VD, PK_1T = PK_1 + (int64_t)VF * VD,
                   PK_2 = PK_1T + (int64_t)VF * VD, PK_2T = PK_2 + (int64_t)VF * VD, PK_LAYER = PK_2T + (int64_t)VF * VD;
-__host__ __device__ inline int64_t al256(int64_t b) { return (b + 255) / 256 * 256; }
 // MXFP8 pack (ewvit_vit_pack_mx, configs[4]): the same eight operand images as e4m3 bytes, each
 // row followed (in a separate array) by its E8M0 scales, one per 32 consecutive elements along
 // the row (the GEMM's K): W [out][in] + S [out][in / 32], W^T [in][out] + S^T [in][out / 32].
@@ -130,71 +129,6 @@ __device__ __forceinline__ MxW mx_image(const void *packed, int m) {
   mx_dims(m, r, c);
   const uint8_t *b = reinterpret_cast<const uint8_t *>(packed) + mx_off(m);
   return MxW{b, b + al256((int64_t)r * c), c};
-}
-template <class F> __host__ __device__ inline int64_t saved_layout(F f) {
-  int64_t o = 0;
-  auto put = [&](int idx, int64_t bytes) { f(idx, o); o += al256(bytes); };
-  put(0, 4 * VRP); put(1, 4 * VRP); put(2, 4 * VRP); put(3, 4 * VRP);
-  put(4, 4 * VRP * VH * 2); put(5, 4 * VRP * VD);
-  put(6, 2 * VRP * VQ); put(7, 2 * VRP * VF); put(8, 2 * VRP * VF);
-  put(9, 2 * VD * VRP); put(10, 2 * VD * VRP); put(11, 2 * VD * VRP); put(12, 2 * VF * VRP);
-  put(13, 4 * VF4_SPLIT * VRP * VD);
-  return o;
-}
-template <class F> __host__ __device__ inline int64_t scratch_layout(F f) {
-  int64_t o = 0;
-  auto put = [&](int idx, int64_t bytes) { f(idx, o); o += al256(bytes); };
-  put(0, 2 * VD * VRP); put(1, 2 * VRP * VF); put(2, 2 * VF * VRP); put(3, 2 * VD * VRP);
-  put(4, 2 * VRP * VQ); put(5, 2 * VQ * VRP);
-  put(6, 4 * VRP * VD); put(7, 4 * VRP * VD); put(8, 4 * VRP * VD);
-  put(9, 4 * 32 * VRP * 2); put(10, 4 * 32 * VRP * 2); put(11, 4 * 2 * VF);
-  return o;
-}
-inline VitSaved vit_saved(void *base) {
-  VitSaved s;
-  char *b = reinterpret_cast<char *>(base);
-  saved_layout([&](int i, int64_t o) {
-    void *q = b + o;
-    switch (i) {
-      case 0: s.mu1 = (float *)q; break;
-      case 1: s.rs1 = (float *)q; break;
-      case 2: s.mu2 = (float *)q; break;
-      case 3: s.rs2 = (float *)q; break;
-      case 4: s.p = (float *)q; break;
-      case 5: s.x1 = (float *)q; break;
-      case 6: s.qkv = (bf16_t *)q; break;
-      case 7: s.aux = (bf16_t *)q; break;
-      case 8: s.h = (bf16_t *)q; break;
-      case 9: s.ln1T = (bf16_t *)q; break;
-      case 10: s.oT = (bf16_t *)q; break;
-      case 11: s.ln2T = (bf16_t *)q; break;
-      case 12: s.hT = (bf16_t *)q; break;
-      default: s.ws2 = (float *)q; break;
-    }
-  });
-  return s;
-}
-inline VitScratch vit_scratch(void *base) {
-  VitScratch s;
-  char *b = reinterpret_cast<char *>(base);
-  scratch_layout([&](int i, int64_t o) {
-    void *q = b + o;
-    switch (i) {
-      case 0: s.gT = (bf16_t *)q; break;
-      case 1: s.g1 = (bf16_t *)q; break;
-      case 2: s.g1T = (bf16_t *)q; break;
-      case 3: s.goT = (bf16_t *)q; break;
-      case 4: s.dqkv = (bf16_t *)q; break;
-      case 5: s.dqkvT = (bf16_t *)q; break;
-      case 6: s.dln2 = (float *)q; break;
-      case 7: s.dx1 = (float *)q; break;
-      case 8: s.dln1 = (float *)q; break;
-      case 9: s.rp2 = (float *)q; break;
-      case 10: s.rp1 = (float *)q; break;
-      default: s.db1p = (float *)q; break;
-    }
-  });
-  return s;
 }
 
 // ---------------------------------------------------------------- shared pieces
@@ -237,39 +171,20 @@ __device__ __forceinline__ void wgrad_block(const bf16_t *AT, const bf16_t *BT, 
                                             int c0, int w, int lane) {
   const int li = lane & 15, lq = lane >> 4;
   const int rb = r0 + (w >> 1) * 32, cb = c0 + (w & 1) * 32;
-  if constexpr (MX) {
-    MxFrag fa[2], fb[2];
+  constexpr int NU = frag_steps<MX>;
+  frag_t<MX> a[NU][2], b[NU][2];
+#pragma unroll
+  for (int u = 0; u < NU; ++u)
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      float va[32], vb[32];
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int k = (hh ? mx_k1(lane) : mx_k0(lane)) + 8 * q;
-          unpack8(ld8b(AT + (int64_t)(rb + t * 16 + li) * VRP + k), va + hh * 16 + q * 8);
-          unpack8(ld8b(BT + (int64_t)(cb + t * 16 + li) * VRP + k), vb + hh * 16 + q * 8);
-        }
-      fa[t] = mx_quant(va);
-      fb[t] = mx_quant(vb);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const vf4 acc = mx_mma(fa[i], fb[j], vf4{0.f, 0.f, 0.f, 0.f});
-#pragma unroll
-        for (int e = 0; e < 4; ++e) out[(int64_t)(rb + i * 16 + lq * 4 + e) * ldo + cb + j * 16 + li] = acc[e];
+      const bf16_t *ar = AT + (int64_t)(rb + t * 16 + li) * VRP, *br = BT + (int64_t)(cb + t * 16 + li) * VRP;
+      if constexpr (MX) {
+        a[u][t] = mx_fill([&](int k, float *v) { unpack8(ld8b(ar + k), v); });
+        b[u][t] = mx_fill([&](int k, float *v) { unpack8(ld8b(br + k), v); });
+      } else {
+        a[u][t] = ld8b(ar + u * 32 + lq * 8);
+        b[u][t] = ld8b(br + u * 32 + lq * 8);
       }
-    return;
-  }
-  vb8 a[4][2], b[4][2];
-#pragma unroll
-  for (int s = 0; s < 4; ++s)
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      a[s][t] = ld8b(AT + (int64_t)(rb + t * 16 + li) * VRP + s * 32 + lq * 8);
-      b[s][t] = ld8b(BT + (int64_t)(cb + t * 16 + li) * VRP + s * 32 + lq * 8);
     }
   vf4 acc[2][2];
 #pragma unroll
@@ -277,17 +192,80 @@ __device__ __forceinline__ void wgrad_block(const bf16_t *AT, const bf16_t *BT, 
 #pragma unroll
     for (int j = 0; j < 2; ++j) acc[i][j] = vf4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int s = 0; s < 4; ++s)
+  for (int u = 0; u < NU; ++u)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = mma(a[s][i], b[s][j], acc[i][j]);
+      for (int j = 0; j < 2; ++j) acc[i][j] = mma(a[u][i], b[u][j], acc[i][j]);
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int e = 0; e < 4; ++e) out[(int64_t)(rb + i * 16 + lq * 4 + e) * ldo + cb + j * 16 + li] = acc[i][j][e];
+}
+
+// The 64-row x 32-column, K = 512 tile of F1 / F3 / B1 (and, in its own copy, F2) on 512 threads:
+// wave (rg = w & 1, kq = w >> 1) owns rows 32 rg .. + 32 of the workgroup's 64 (two row tiles t) x the two column
+// tiles c0 .., c0 + 16 .. and the K quarter kq (one batch of loads: 4 k-steps or one MX step).
+// a8(t, k, v): the 8 fp32 A values of the lane's row of row tile t at k .. k + 7, zeros past R;
+// B from the packed weight image, W [c][512] bf16 or its MX form W8.  The quarters meet in red
+// and are added as ((kq 0 + 1) + 2) + 3 by the kq == 0 waves, which hand each sum to epi(i, j, y):
+// row tile i, column tile j, y[e] at row 4 (lane >> 4) + e, column lane & 15 (read as it is
+// needed: all 16 sums up front cost B1 two waves per SIMD).  Returns whether the wave was one of
+// them, to all waves and past the barrier.
+template <bool MX, class AF, class EF>
+__device__ __forceinline__ bool tile64x32(AF a8, const bf16_t *W, const MxW &W8, int c0, vf4 (&red)[3][2][2][2][64],
+                                          EF epi) {
+  constexpr int NU = frag_steps<MX>;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int rg = w & 1, kq = w >> 1, li = lane & 15, lq = lane >> 4;
+  frag_t<MX> af[NU][2], bf[NU][2];
+#pragma unroll
+  for (int u = 0; u < NU; ++u)
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      const int n = c0 + t * 16 + li;
+      if constexpr (MX) {
+        af[u][t] = mx_fill([&](int k, float *v) { a8(t, kq * 128 + k, v); });
+        bf[u][t] = mx_load(W8.row(n), kq * 128, W8.srow(n));
+      } else {
+        const int k = kq * 128 + u * 32 + lq * 8;
+        float v[8];
+        a8(t, k, v);
+        af[u][t] = pack8(v);
+        bf[u][t] = ld8b(W + (int64_t)n * VD + k);
+      }
+    }
+  vf4 acc[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) acc[i][j] = vf4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < NU; ++u)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) acc[i][j] = mma(af[u][i], bf[u][j], acc[i][j]);
+  if (kq > 0)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) red[kq - 1][rg][i][j][lane] = acc[i][j];
+  __syncthreads();
+  if (kq > 0) return false;
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const vf4 a = red[0][rg][i][j][lane], b = red[1][rg][i][j][lane], c = red[2][rg][i][j][lane];
+      float y[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) y[e] = ((acc[i][j][e] + a[e]) + b[e]) + c[e];
+      epi(i, j, y);
+    }
+  return true;
 }
 
 // ---------------------------------------------------------------- F1 / F3: LN + GEMM
@@ -325,8 +303,9 @@ __global__ __launch_bounds__(512) void vit_ln_gemm_kernel(VitP p, int R, const f
     }
     *reinterpret_cast<vb8 *>(lnT + (int64_t)k * VRP + r0) = pack8(v);
   }
-  const int rg = w & 1, kq = w >> 1, li = lane & 15, lq = lane >> 4;
+  const int rg = w & 1, li = lane & 15, lq = lane >> 4;
   const int c0 = cb * 32;
+  const MxW W8 = MX ? mx_image(p.packed, MODE ? 4 : 0) : MxW{nullptr, nullptr, 0};
   int row[2];
   float mu[2], rs[2];
 #pragma unroll
@@ -335,103 +314,39 @@ __global__ __launch_bounds__(512) void vit_ln_gemm_kernel(VitP p, int R, const f
     mu[t] = smu[row[t]];
     rs[t] = srs[row[t]];
   }
-  vf4 acc[2][2];
+  auto a8 = [&](int t, int k, float *v) {
+    float g8[8], b8[8];
+    ld8f(gw + k, g8);
+    ld8f(gb + k, b8);
+    ld8f(xin + (int64_t)rclamp(row[t], R) * VD + k, v);
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+    for (int e = 0; e < 8; ++e) v[e] = row[t] < R ? (v[e] - mu[t]) * rs[t] * g8[e] + b8[e] : 0.f;
+  };
+  tile64x32<MX>(a8, W, W8, c0, red, [&](int i, int j, const float *v4) {
+    const int col = c0 + j * 16 + li;
+    const int rb = rbase + rg * 32 + i * 16 + lq * 4;
+    if (MODE == 0) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = vf4{0.f, 0.f, 0.f, 0.f};
-  if constexpr (MX) {
-    // the wave's K quarter is one 128-wide MX step: LN output quantized from fp32 in registers
-    const MxW W8 = mx_image(p.packed, MODE ? 4 : 0);
-    MxFrag af[2], bf[2];
+      for (int e = 0; e < 4; ++e)
+        if (rb + e < R) s.qkv[(int64_t)(rb + e) * VQ + col] = f2bf(v4[e]);
+    } else {
+      const float bias = p.b1[col];
+      float hv[4];
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      float v[32];
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int k = kq * 128 + (hh ? mx_k1(lane) : mx_k0(lane)) + 8 * q;
-          float g8[8], b8[8], x8[8];
-          ld8f(gw + k, g8);
-          ld8f(gb + k, b8);
-          ld8f(xin + (int64_t)rclamp(row[t], R) * VD + k, x8);
-#pragma unroll
-          for (int e = 0; e < 8; ++e)
-            v[hh * 16 + q * 8 + e] = row[t] < R ? (x8[e] - mu[t]) * rs[t] * g8[e] + b8[e] : 0.f;
+      for (int e = 0; e < 4; ++e) {
+        const float pre = v4[e] + bias;
+        hv[e] = rb + e < R ? gelu_erf(pre) : 0.f;
+        if (rb + e < R) {
+          s.aux[(int64_t)(rb + e) * VF + col] = f2bf(pre);
+          s.h[(int64_t)(rb + e) * VF + col] = f2bf(hv[e]);
         }
-      af[t] = mx_quant(v);
-      const int n = c0 + t * 16 + li;
-      bf[t] = mx_load(W8.row(n), kq * 128, W8.srow(n));
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = mx_mma(af[i], bf[j], acc[i][j]);
-  } else {
-    vb8 af[4][2], bf[4][2];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int k = kq * 128 + u * 32 + lq * 8;
-      float g8[8], b8[8];
-      ld8f(gw + k, g8);
-      ld8f(gb + k, b8);
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        float v[8];
-        ld8f(xin + (int64_t)rclamp(row[t], R) * VD + k, v);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = row[t] < R ? (v[e] - mu[t]) * rs[t] * g8[e] + b8[e] : 0.f;
-        af[u][t] = pack8(v);
-        bf[u][t] = ld8b(W + (int64_t)(c0 + t * 16 + li) * VD + k);
       }
+      uint2 pk;
+      pk.x = (unsigned)f2bf(hv[0]) | ((unsigned)f2bf(hv[1]) << 16);
+      pk.y = (unsigned)f2bf(hv[2]) | ((unsigned)f2bf(hv[3]) << 16);
+      *reinterpret_cast<uint2 *>(s.hT + (int64_t)col * VRP + rb) = pk;
     }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = mma(af[u][i], bf[u][j], acc[i][j]);
-  }
-  if (kq > 0)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) red[kq - 1][rg][i][j][lane] = acc[i][j];
-  __syncthreads();
-  if (kq > 0) return;
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const vf4 a = red[0][rg][i][j][lane], b = red[1][rg][i][j][lane], c = red[2][rg][i][j][lane];
-      const int col = c0 + j * 16 + li;
-      const int rb = rbase + rg * 32 + i * 16 + lq * 4;
-      float v4[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) v4[e] = ((acc[i][j][e] + a[e]) + b[e]) + c[e];
-      if (MODE == 0) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (rb + e < R) s.qkv[(int64_t)(rb + e) * VQ + col] = f2bf(v4[e]);
-      } else {
-        const float bias = p.b1[col];
-        float hv[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float pre = v4[e] + bias;
-          hv[e] = rb + e < R ? gelu_erf(pre) : 0.f;
-          if (rb + e < R) {
-            s.aux[(int64_t)(rb + e) * VF + col] = f2bf(pre);
-            s.h[(int64_t)(rb + e) * VF + col] = f2bf(hv[e]);
-          }
-        }
-        uint2 pk;
-        pk.x = (unsigned)f2bf(hv[0]) | ((unsigned)f2bf(hv[1]) << 16);
-        pk.y = (unsigned)f2bf(hv[2]) | ((unsigned)f2bf(hv[3]) << 16);
-        *reinterpret_cast<uint2 *>(s.hT + (int64_t)col * VRP + rb) = pk;
-      }
-    }
+  });
 }
 
 // ---------------------------------------------------------------- F2: attention + to_out
@@ -508,6 +423,8 @@ __global__ __launch_bounds__(512) void vit_attn_proj_kernel(VitP p, int R, const
     }
     *reinterpret_cast<vb8 *>(s.oT + (int64_t)k * VRP + r0) = pack8(v);
   }
+  // its own copy of tile64x32: with the A expression in a lambda the MX form took 171 VGPRs for 165,
+  // 2 waves per SIMD for 3
   const int rg = w & 1, kq = w >> 1, li = lane & 15, lq = lane >> 4;
   const int c0 = cb * 32;
   vf4 acc[2][2];
@@ -637,95 +554,39 @@ __global__ __launch_bounds__(512) void vit_mlp2_bwd_kernel(VitP p, VitG G, int R
       G.b2[jb * 8 + tid] = a;
     }
   }
-  const int rg = w & 1, kq = w >> 1, li = lane & 15, lq = lane >> 4;
-  vf4 acc[2][2];
+  const int rg = w & 1, li = lane & 15, lq = lane >> 4;
+  const MxW W8 = MX ? mx_image(p.packed, 7) : MxW{nullptr, nullptr, 0};     // W2^T [2048][512]
+  auto a8 = [&](int t, int k, float *v) {
+    const int r = rbase + rg * 32 + t * 16 + li;
+    ld8f(g + (int64_t)rclamp(r, R) * VD + k, v);
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+    for (int e = 0; e < 8; ++e) v[e] = r < R ? v[e] : 0.f;
+  };
+  float cs[2] = {0.f, 0.f};
+  const bool summed = tile64x32<MX>(a8, wT, W8, J0, red, [&](int i, int j, const float *dhf) {
+    const int col = J0 + j * 16 + li;
+    const int rb = rbase + rg * 32 + i * 16 + lq * 4;
+    float gv[4];
 #pragma unroll
-    for (int j = 0; j < 2; ++j) acc[i][j] = vf4{0.f, 0.f, 0.f, 0.f};
-  if constexpr (MX) {
-    const MxW W8 = mx_image(p.packed, 7);         // W2^T [2048][512]
-    MxFrag af[2], bf[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int r = rbase + rg * 32 + t * 16 + li;
-      float v[32];
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int k = kq * 128 + (hh ? mx_k1(lane) : mx_k0(lane)) + 8 * q;
-          ld8f(g + (int64_t)rclamp(r, R) * VD + k, v + hh * 16 + q * 8);
-        }
-      if (r >= R)
-#pragma unroll
-        for (int e = 0; e < 32; ++e) v[e] = 0.f;
-      af[t] = mx_quant(v);
-      const int n = J0 + t * 16 + li;
-      bf[t] = mx_load(W8.row(n), kq * 128, W8.srow(n));
+    for (int e = 0; e < 4; ++e) {
+      const int r = rb + e;
+      const float a = bf2f(s.aux[(int64_t)rclamp(r, R) * VF + col]);
+      const float dh = rbf(dhf[e]);
+      gv[e] = r < R ? dh * gelu_erf_grad(a) : 0.f;
+      if (r < R) z.g1[(int64_t)r * VF + col] = f2bf(gv[e]);
+      cs[j] += gv[e];
     }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc[i][j] = mx_mma(af[i], bf[j], acc[i][j]);
-  } else {
-    vb8 af[4][2], bf[4][2];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int k = kq * 128 + u * 32 + lq * 8;
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const int r = rbase + rg * 32 + t * 16 + li;
-        float v[8];
-        ld8f(g + (int64_t)rclamp(r, R) * VD + k, v);
-        af[u][t] = pack8(v);
-        if (r >= R) af[u][t] = zero8();
-        bf[u][t] = ld8b(wT + (int64_t)(J0 + t * 16 + li) * VD + k);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = mma(af[u][i], bf[u][j], acc[i][j]);
-  }
-  if (kq > 0)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) red[kq - 1][rg][i][j][lane] = acc[i][j];
-  __syncthreads();
-  if (kq == 0) {
-    float cs[2] = {0.f, 0.f};
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const vf4 ra = red[0][rg][i][j][lane], rb2 = red[1][rg][i][j][lane], rc = red[2][rg][i][j][lane];
-        const int col = J0 + j * 16 + li;
-        const int rb = rbase + rg * 32 + i * 16 + lq * 4;
-        float gv[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int r = rb + e;
-          const float a = bf2f(s.aux[(int64_t)rclamp(r, R) * VF + col]);
-          const float dh = rbf(((acc[i][j][e] + ra[e]) + rb2[e]) + rc[e]);
-          gv[e] = r < R ? dh * gelu_erf_grad(a) : 0.f;
-          if (r < R) z.g1[(int64_t)r * VF + col] = f2bf(gv[e]);
-          cs[j] += gv[e];
-        }
-        uint2 pk;
-        pk.x = (unsigned)f2bf(gv[0]) | ((unsigned)f2bf(gv[1]) << 16);
-        pk.y = (unsigned)f2bf(gv[2]) | ((unsigned)f2bf(gv[3]) << 16);
-        *reinterpret_cast<uint2 *>(z.g1T + (int64_t)col * VRP + rb) = pk;
-      }
+    uint2 pk;
+    pk.x = (unsigned)f2bf(gv[0]) | ((unsigned)f2bf(gv[1]) << 16);
+    pk.y = (unsigned)f2bf(gv[2]) | ((unsigned)f2bf(gv[3]) << 16);
+    *reinterpret_cast<uint2 *>(z.g1T + (int64_t)col * VRP + rb) = pk;
+  });
+  if (summed)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const float v = rows_sum4(cs[j]);
       if (lq == 0) scol[rg][j * 16 + li] = v;
     }
-  }
   __syncthreads();
   // this row half's Linear1 bias-gradient partial (B2 adds the halves)
   if (tid < 32) z.db1p[rh * VF + J0 + tid] = scol[0][tid] + scol[1][tid];
@@ -742,54 +603,38 @@ template <int K, bool MX>
 __device__ __forceinline__ void dgrad_block(const bf16_t *A, const bf16_t *BT, const MxW &BT8, float *out, int R,
                                             int I0, int rq, int w, int lane, vf4 *red, const float *X,
                                             const float *mu, const float *rs, const float *gamma, float *rpart) {
-  constexpr int KQ = K / 4, NS = KQ / 32;
+  constexpr int KQ = K / 4, NS = KQ / 32, NU = frag_steps<MX>;
   const int li = lane & 15, lq = lane >> 4;
   vf4 acc[2];
   acc[0] = acc[1] = vf4{0.f, 0.f, 0.f, 0.f};
-  if constexpr (MX) {
 #pragma unroll 1
-    for (int sb = 0; sb < NS; sb += 4) {
-      const int kb = w * KQ + sb * 32;
-      MxFrag af[2];
+  for (int sb = 0; sb < NS; sb += 4) {
+    const int kb = w * KQ + sb * 32;             // 128 of K per trip
+    frag_t<MX> af[NU][2], bf[NU];
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         const int r = rq * 32 + t * 16 + li;
-        float v[32];
+        const bf16_t *ar = A + (int64_t)rclamp(r, R) * K + kb;
+        if constexpr (MX) {
+          af[u][t] = mx_fill([&](int k, float *v) {
+            unpack8(ld8b(ar + k), v);
 #pragma unroll
-        for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-          for (int q = 0; q < 2; ++q)
-            unpack8(ld8b(A + (int64_t)rclamp(r, R) * K + kb + (hh ? mx_k1(lane) : mx_k0(lane)) + 8 * q),
-                    v + hh * 16 + q * 8);
-        if (r >= R)
-#pragma unroll
-          for (int e = 0; e < 32; ++e) v[e] = 0.f;
-        af[t] = mx_quant(v);
-      }
-      const MxFrag bf = mx_load(BT8.row(I0 + li), kb, BT8.srow(I0 + li));
-#pragma unroll
-      for (int t = 0; t < 2; ++t) acc[t] = mx_mma(af[t], bf, acc[t]);
-    }
-  } else {
-#pragma unroll 1
-    for (int sb = 0; sb < NS; sb += 4) {
-      vb8 af[4][2], bf[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int k = w * KQ + (sb + u) * 32 + lq * 8;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-          const int r = rq * 32 + t * 16 + li;
-          af[u][t] = ld8b(A + (int64_t)rclamp(r, R) * K + k);
+            for (int e = 0; e < 8; ++e) v[e] = r < R ? v[e] : 0.f;
+          });
+        } else {
+          af[u][t] = ld8b(ar + u * 32 + lq * 8);
           if (r >= R) af[u][t] = zero8();
         }
-        bf[u] = ld8b(BT + (int64_t)(I0 + li) * K + k);
       }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) acc[t] = mma(af[u][t], bf[u], acc[t]);
+      if constexpr (MX) bf[u] = mx_load(BT8.row(I0 + li), kb, BT8.srow(I0 + li));
+      else bf[u] = ld8b(BT + (int64_t)(I0 + li) * K + kb + u * 32 + lq * 8);
     }
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+#pragma unroll
+      for (int t = 0; t < 2; ++t) acc[t] = mma(af[u][t], bf[u], acc[t]);
   }
   if (w > 0)
 #pragma unroll
@@ -945,34 +790,28 @@ __global__ __launch_bounds__(512) void vit_ln2_bwd_attn_kernel(VitP p, VitG G, i
     mb[t] = sbm[row[t]];
   }
   constexpr int NSL = MX ? 4 : 8;                  // K slices added in the reduction below
+  // g_o at row tile t, k .. k + 7: LN2 backward + residual, times to_out's dropout mask
+  auto go8 = [&](int t, int k, float *v) {
+    const int r = row[t], rr = rclamp(r, R);
+    float gm[8], d[8], x[8], gg[8];
+    ld8f(p.ln2_w + k, gm);
+    ld8f(z.dln2 + (int64_t)rr * VD + k, d);
+    ld8f(s.x1 + (int64_t)rr * VD + k, x);
+    ld8f(g + (int64_t)rr * VD + k, gg);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float xh = (x[e] - mu[t]) * rs[t];
+      float dx = rs[t] * (gm[e] * d[e] - ma[t] - xh * mb[t]) + gg[e];
+      if (p.drop_p > 0.f) dx *= keep_scale(p.drop_p, sd, (uint64_t)(r * VD + k + e));
+      v[e] = r < R ? dx : 0.f;
+    }
+  };
   if constexpr (MX) {
     const MxW W8 = mx_image(p.packed, 3);          // Wo^T [512][512]
     const int ks = w & 3, ch = w >> 2;
     MxFrag af[2], bf[2];
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      const int r = row[t], rr = rclamp(r, R);
-      float v[32];
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const int k = ks * 128 + (hh ? mx_k1(lane) : mx_k0(lane)) + 8 * q;
-          float gm[8], d[8], x[8], gg[8];
-          ld8f(p.ln2_w + k, gm);
-          ld8f(z.dln2 + (int64_t)rr * VD + k, d);
-          ld8f(s.x1 + (int64_t)rr * VD + k, x);
-          ld8f(g + (int64_t)rr * VD + k, gg);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float xh = (x[e] - mu[t]) * rs[t];
-            float dx = rs[t] * (gm[e] * d[e] - ma[t] - xh * mb[t]) + gg[e];
-            if (p.drop_p > 0.f) dx *= keep_scale(p.drop_p, sd, (uint64_t)(r * VD + k + e));
-            v[hh * 16 + q * 8 + e] = r < R ? dx : 0.f;
-          }
-        }
-      af[t] = mx_quant(v);
-    }
+    for (int t = 0; t < 2; ++t) af[t] = mx_fill([&](int k, float *v) { go8(t, ks * 128 + k, v); });
 #pragma unroll
     for (int jj = 0; jj < 2; ++jj) {
       const int n = h * VDH + (ch * 2 + jj) * 16 + li;
@@ -983,48 +822,34 @@ __global__ __launch_bounds__(512) void vit_ln2_bwd_attn_kernel(VitP p, VitG G, i
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) red[ks][i][ch * 2 + jj][lane] = mx_mma(af[i], bf[jj], vf4{0.f, 0.f, 0.f, 0.f});
   } else {
-  vf4 acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = vf4{0.f, 0.f, 0.f, 0.f};
-  {
     vb8 af[2][2], bf[2][4];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int k = w * 64 + u * 32 + lq * 8;
-      float gm[8];
-      ld8f(p.ln2_w + k, gm);
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
-        const int r = row[t], rr = rclamp(r, R);
-        float d[8], x[8], gg[8], v[8];
-        ld8f(z.dln2 + (int64_t)rr * VD + k, d);
-        ld8f(s.x1 + (int64_t)rr * VD + k, x);
-        ld8f(g + (int64_t)rr * VD + k, gg);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float xh = (x[e] - mu[t]) * rs[t];
-          float dx = rs[t] * (gm[e] * d[e] - ma[t] - xh * mb[t]) + gg[e];
-          if (p.drop_p > 0.f) dx *= keep_scale(p.drop_p, sd, (uint64_t)(r * VD + k + e));
-          v[e] = r < R ? dx : 0.f;
-        }
+        float v[8];
+        go8(t, k, v);
         af[u][t] = pack8(v);
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j) bf[u][j] = ld8b(wT + (int64_t)(h * VDH + j * 16 + li) * VD + k);
     }
+    vf4 acc[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[i][j] = vf4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int u = 0; u < 2; ++u)
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = mma(af[u][i], bf[u][j], acc[i][j]);
-  }
 #pragma unroll
-  for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) red[w][i][j][lane] = acc[i][j];
+      for (int j = 0; j < 4; ++j) red[w][i][j][lane] = acc[i][j];
   }
   __syncthreads();
   if (tid < 2 * 4 * 64) {
@@ -1204,20 +1029,36 @@ __global__ __launch_bounds__(512) void vit_embed_bwd_kernel(const float *dtok, i
 // ---------------------------------------------------------------- weight pack (once per step)
 // a workgroup per 64 x 64 tile of one weight: fp32 [out][in] -> bf16 [out][in] and [in][out]
 struct VitPackSrc { const float *w[4 * EWVIT_VIT_PACK_MAX]; };
+// tiles per layer: qkv 24 x 8, o 8 x 8, w1 32 x 8, w2 8 x 32
+constexpr int PK_T0 = 24 * 8, PK_T1 = PK_T0 + 64, PK_T2 = PK_T1 + 256, PK_TILES = PK_T2 + 256;
+// the workgroup's tile: weight m (0..3: qkv, o, 1, 2) of its layer, W [rows][cols], tile origin
+struct PackTile {
+  const float *W;
+  int layer, m, rows, cols, r0, c0;
+};
+__device__ __forceinline__ PackTile pack_tile(const VitPackSrc &src) {
+  PackTile k;
+  const int t = blockIdx.x % PK_TILES;
+  int tr, tc;
+  if (t < PK_T0) { k.m = 0; tr = t / 8; tc = t % 8; }
+  else if (t < PK_T1) { k.m = 1; tr = (t - PK_T0) / 8; tc = (t - PK_T0) % 8; }
+  else if (t < PK_T2) { k.m = 2; tr = (t - PK_T1) / 8; tc = (t - PK_T1) % 8; }
+  else { k.m = 3; tr = (t - PK_T2) / 32; tc = (t - PK_T2) % 32; }
+  k.layer = blockIdx.x / PK_TILES;
+  mx_dims(2 * k.m, k.rows, k.cols);
+  k.W = src.w[k.layer * 4 + k.m];
+  k.r0 = tr * 64;
+  k.c0 = tc * 64;
+  return k;
+}
 __global__ __launch_bounds__(256) void vit_pack_kernel(VitPackSrc src, int nlayers, bf16_t *packed) {
   __shared__ float tile[64][65];
-  // tiles per layer: qkv 24 x 8, o 8 x 8, w1 32 x 8, w2 8 x 32
-  constexpr int T0 = 24 * 8, T1 = T0 + 64, T2 = T1 + 256, TL = T2 + 256;
-  const int layer = blockIdx.x / TL, t = blockIdx.x % TL;
-  int m, tr, tc, rows, cols;
-  int64_t off, offT;
-  if (t < T0) { m = 0; tr = t / 8; tc = t % 8; rows = VQ; cols = VD; off = PK_QKV; offT = PK_QKVT; }
-  else if (t < T1) { m = 1; tr = (t - T0) / 8; tc = (t - T0) % 8; rows = VD; cols = VD; off = PK_O; offT = PK_OT; }
-  else if (t < T2) { m = 2; tr = (t - T1) / 8; tc = (t - T1) % 8; rows = VF; cols = VD; off = PK_1; offT = PK_1T; }
-  else { m = 3; tr = (t - T2) / 32; tc = (t - T2) % 32; rows = VD; cols = VF; off = PK_2; offT = PK_2T; }
-  const float *W = src.w[layer * 4 + m];
-  bf16_t *dst = packed + (int64_t)layer * PK_LAYER;
-  const int tid = threadIdx.x, r0 = tr * 64, c0 = tc * 64;
+  const PackTile k = pack_tile(src);
+  const float *W = k.W;
+  const int tid = threadIdx.x, r0 = k.r0, c0 = k.c0, rows = k.rows, cols = k.cols;
+  // W's image, W^T's right after it
+  const int64_t off = k.m == 0 ? PK_QKV : k.m == 1 ? PK_O : k.m == 2 ? PK_1 : PK_2, offT = off + (int64_t)rows * cols;
+  bf16_t *dst = packed + (int64_t)k.layer * PK_LAYER;
   float4 v[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
@@ -1243,7 +1084,6 @@ __global__ __launch_bounds__(256) void vit_pack_kernel(VitPackSrc src, int nlaye
     pk.y = (unsigned)f2bf(tile[4 * q + 2][c]) | ((unsigned)f2bf(tile[4 * q + 3][c]) << 16);
     *reinterpret_cast<uint2 *>(dst + offT + (int64_t)(c0 + c) * rows + r0 + 4 * q) = pk;
   }
-  (void)rows;
 }
 
 // MXFP8 pack: the same 64 x 64 tiles; threads 0..127 quantize the tile's 64 rows x 2 blocks of
@@ -1251,18 +1091,10 @@ __global__ __launch_bounds__(256) void vit_pack_kernel(VitPackSrc src, int nlaye
 // straight from the fp32 masters (one rounding)
 __global__ __launch_bounds__(256) void vit_pack_mx_kernel(VitPackSrc src, int nlayers, uint8_t *packed) {
   __shared__ float tile[64][65];
-  constexpr int T0 = 24 * 8, T1 = T0 + 64, T2 = T1 + 256, TL = T2 + 256;
-  const int layer = blockIdx.x / TL, t = blockIdx.x % TL;
-  int m, tr, tc;
-  if (t < T0) { m = 0; tr = t / 8; tc = t % 8; }
-  else if (t < T1) { m = 1; tr = (t - T0) / 8; tc = (t - T0) % 8; }
-  else if (t < T2) { m = 2; tr = (t - T1) / 8; tc = (t - T1) % 8; }
-  else { m = 3; tr = (t - T2) / 32; tc = (t - T2) % 32; }
-  int rows, cols;
-  mx_dims(2 * m, rows, cols);
-  const float *W = src.w[layer * 4 + m];
-  uint8_t *base = packed + (int64_t)layer * mx_off(8);
-  const int tid = threadIdx.x, r0 = tr * 64, c0 = tc * 64;
+  const PackTile k = pack_tile(src);
+  const float *W = k.W;
+  const int tid = threadIdx.x, m = k.m, r0 = k.r0, c0 = k.c0, rows = k.rows, cols = k.cols;
+  uint8_t *base = packed + (int64_t)k.layer * mx_off(8);
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const int i = tid + u * 256, r = i >> 4, q = i & 15;
@@ -1300,36 +1132,36 @@ using namespace ewvit;
 extern "C" int64_t ewvit_vit_layer_workspace(int which) {
   if (which == 3) return mx_off(8);
   if (which == 2) return PK_LAYER * 2;
-  return which == 0 ? saved_layout([](int, int64_t) {}) : scratch_layout([](int, int64_t) {});
+  int64_t bytes;
+  if (which == 0) vit_carve<VitSaved>(nullptr, &bytes);
+  else vit_carve<VitScratch>(nullptr, &bytes);
+  return bytes;
+}
+
+// the fp32 masters of n layers for either pack kernel
+static int vit_pack_src(const char *what, const ewvit_vit_layer *layers, int n, const void *packed, VitPackSrc *src) {
+  EWVIT_CHECK_ARG(layers && packed && n >= 1 && n <= EWVIT_VIT_PACK_MAX, "%s: n=%d", what, n);
+  for (int i = 0; i < n; ++i) {
+    EWVIT_CHECK_ARG(layers[i].wqkv && layers[i].wo && layers[i].w1 && layers[i].w2, "%s: null weight", what);
+    src->w[4 * i] = layers[i].wqkv;
+    src->w[4 * i + 1] = layers[i].wo;
+    src->w[4 * i + 2] = layers[i].w1;
+    src->w[4 * i + 3] = layers[i].w2;
+  }
+  return 0;
 }
 
 extern "C" int ewvit_vit_pack(const ewvit_vit_layer *layers, int n, void *packed, void *stream) {
-  EWVIT_CHECK_ARG(layers && packed && n >= 1 && n <= EWVIT_VIT_PACK_MAX, "vit_pack: n=%d", n);
   VitPackSrc src;
-  for (int i = 0; i < n; ++i) {
-    EWVIT_CHECK_ARG(layers[i].wqkv && layers[i].wo && layers[i].w1 && layers[i].w2, "vit_pack: null weight");
-    src.w[4 * i] = layers[i].wqkv;
-    src.w[4 * i + 1] = layers[i].wo;
-    src.w[4 * i + 2] = layers[i].w1;
-    src.w[4 * i + 3] = layers[i].w2;
-  }
-  hipLaunchKernelGGL(vit_pack_kernel, dim3(n * (24 * 8 + 64 + 256 + 256)), dim3(256), 0, as_stream(stream), src, n,
-                     (bf16_t *)packed);
+  if (int rc = vit_pack_src("vit_pack", layers, n, packed, &src)) return rc;
+  hipLaunchKernelGGL(vit_pack_kernel, dim3(n * PK_TILES), dim3(256), 0, as_stream(stream), src, n, (bf16_t *)packed);
   return launch_status("vit_pack");
 }
 
 extern "C" int ewvit_vit_pack_mx(const ewvit_vit_layer *layers, int n, void *packed, void *stream) {
-  EWVIT_CHECK_ARG(layers && packed && n >= 1 && n <= EWVIT_VIT_PACK_MAX, "vit_pack_mx: n=%d", n);
   VitPackSrc src;
-  for (int i = 0; i < n; ++i) {
-    EWVIT_CHECK_ARG(layers[i].wqkv && layers[i].wo && layers[i].w1 && layers[i].w2, "vit_pack_mx: null weight");
-    src.w[4 * i] = layers[i].wqkv;
-    src.w[4 * i + 1] = layers[i].wo;
-    src.w[4 * i + 2] = layers[i].w1;
-    src.w[4 * i + 3] = layers[i].w2;
-  }
-  hipLaunchKernelGGL(vit_pack_mx_kernel, dim3(n * (24 * 8 + 64 + 256 + 256)), dim3(256), 0, as_stream(stream), src,
-                     n, (uint8_t *)packed);
+  if (int rc = vit_pack_src("vit_pack_mx", layers, n, packed, &src)) return rc;
+  hipLaunchKernelGGL(vit_pack_mx_kernel, dim3(n * PK_TILES), dim3(256), 0, as_stream(stream), src, n, (uint8_t *)packed);
   return launch_status("vit_pack_mx");
 }
 
@@ -1347,25 +1179,22 @@ extern "C" int ewvit_vit_layer_fwd(const ewvit_vit_layer *p, int R, const float 
                                    void *stream) {
   if (int rc = vit_check(p, R)) return rc;
   EWVIT_CHECK_ARG(x0 && saved && x2, "vit_layer_fwd: null pointer");
-  const VitSaved s = vit_saved(saved);
+  const VitSaved s = vit_carve<VitSaved>(saved);
   hipStream_t st = as_stream(stream);
-  if (p->mx) {
-    hipLaunchKernelGGL((vit_ln_gemm_kernel<0, true>), dim3(2 * VQ / 32), dim3(512), 0, st, *p, R, x0, s);
-    hipLaunchKernelGGL(vit_attn_proj_kernel<true>, dim3(2 * VD / 32), dim3(512), 0, st, *p, R, x0, s);
-    hipLaunchKernelGGL((vit_ln_gemm_kernel<1, true>), dim3(2 * VF / 32), dim3(512), 0, st, *p, R, (const float *)s.x1, s);
-    if (int rc = launch_status("vit_layer_fwd")) return rc;
-    // Linear2 on the MXFP8 split-K GEMM (W2 block-quantized from the fp32 master as it is
-    // staged: the same e4m3 values and scales as the pack's image 6)
-    return ewvit_gemm_mx8(s.h, EWVIT_BF16, VF, 1, p->w2, EWVIT_F32, 1, VF, x2, EWVIT_F32, VD, R, VD, VF, 1.f, 0.f,
-                          p->b2, 0, nullptr, 0.f, 0, nullptr, s.x1, EWVIT_F32, VD, VF4_SPLIT, s.ws2, stream);
-  }
-  hipLaunchKernelGGL((vit_ln_gemm_kernel<0, false>), dim3(2 * VQ / 32), dim3(512), 0, st, *p, R, x0, s);
-  hipLaunchKernelGGL(vit_attn_proj_kernel<false>, dim3(2 * VD / 32), dim3(512), 0, st, *p, R, x0, s);
-  hipLaunchKernelGGL((vit_ln_gemm_kernel<1, false>), dim3(2 * VF / 32), dim3(512), 0, st, *p, R, (const float *)s.x1, s);
+  by_bool(p->mx, [&](auto mx) {
+    hipLaunchKernelGGL((vit_ln_gemm_kernel<0, mx()>), dim3(2 * VQ / 32), dim3(512), 0, st, *p, R, x0, s);
+    hipLaunchKernelGGL(vit_attn_proj_kernel<mx()>, dim3(2 * VD / 32), dim3(512), 0, st, *p, R, x0, s);
+    hipLaunchKernelGGL((vit_ln_gemm_kernel<1, mx()>), dim3(2 * VF / 32), dim3(512), 0, st, *p, R, (const float *)s.x1, s);
+  });
   if (int rc = launch_status("vit_layer_fwd")) return rc;
   // Linear2 + bias + residual: K = 2048 against 128 rows wants its K split over many
   // workgroups (one workgroup per column block reading all of h measured 32 us): the split-K
-  // MFMA GEMM with the packed bf16 W2, its reduce adding b2 and x1
+  // GEMM, its reduce adding b2 and x1 — MFMA bf16 with the packed bf16 W2, or MXFP8 with W2
+  // block-quantized from the fp32 master as it is staged (the same e4m3 values and scales as
+  // the pack's image 6)
+  if (p->mx)
+    return ewvit_gemm_mx8(s.h, EWVIT_BF16, VF, 1, p->w2, EWVIT_F32, 1, VF, x2, EWVIT_F32, VD, R, VD, VF, 1.f, 0.f,
+                          p->b2, 0, nullptr, 0.f, 0, nullptr, s.x1, EWVIT_F32, VD, VF4_SPLIT, s.ws2, stream);
   return ewvit_gemm(s.h, EWVIT_BF16, VF, 1, reinterpret_cast<const bf16_t *>(p->packed) + PK_2, EWVIT_BF16, 1, VF,
                     x2, EWVIT_F32, VD, R, VD, VF, 1.f, 0.f, p->b2, 0, nullptr, 0.f, 0, nullptr, s.x1, EWVIT_F32, VD,
                     VF4_SPLIT, s.ws2, stream);
@@ -1379,20 +1208,15 @@ extern "C" int ewvit_vit_layer_bwd(const ewvit_vit_layer *p, int R, const float 
   EWVIT_CHECK_ARG(G->ln1_w && G->ln1_b && G->wqkv && G->wo && G->bo && G->ln2_w && G->ln2_b && G->w1 && G->b1 &&
                       G->w2 && G->b2,
                   "vit_layer_bwd: null gradient");
-  const VitSaved s = vit_saved(const_cast<void *>(saved));
-  const VitScratch z = vit_scratch(scratch);
+  const VitSaved s = vit_carve<VitSaved>(const_cast<void *>(saved));
+  const VitScratch z = vit_carve<VitScratch>(scratch);
   hipStream_t st = as_stream(stream);
-  if (p->mx) {
-    hipLaunchKernelGGL(vit_mlp2_bwd_kernel<true>, dim3(2 * VF / 32), dim3(512), 0, st, *p, *G, R, g, s, z);
-    hipLaunchKernelGGL(vit_mlp1_bwd_kernel<true>, dim3(128 + 256 + 256 + VF / 256), dim3(256), 0, st, *p, *G, R, s, z);
-    hipLaunchKernelGGL(vit_ln2_bwd_attn_kernel<true>, dim3(4 * VH + 16), dim3(512), 0, st, *p, *G, R, g, s, z);
-    hipLaunchKernelGGL(vit_qkv_bwd_kernel<true>, dim3(128 + 192 + 64), dim3(256), 0, st, *p, *G, R, x0, s, z);
-  } else {
-    hipLaunchKernelGGL(vit_mlp2_bwd_kernel<false>, dim3(2 * VF / 32), dim3(512), 0, st, *p, *G, R, g, s, z);
-    hipLaunchKernelGGL(vit_mlp1_bwd_kernel<false>, dim3(128 + 256 + 256 + VF / 256), dim3(256), 0, st, *p, *G, R, s, z);
-    hipLaunchKernelGGL(vit_ln2_bwd_attn_kernel<false>, dim3(4 * VH + 16), dim3(512), 0, st, *p, *G, R, g, s, z);
-    hipLaunchKernelGGL(vit_qkv_bwd_kernel<false>, dim3(128 + 192 + 64), dim3(256), 0, st, *p, *G, R, x0, s, z);
-  }
+  by_bool(p->mx, [&](auto mx) {
+    hipLaunchKernelGGL(vit_mlp2_bwd_kernel<mx()>, dim3(2 * VF / 32), dim3(512), 0, st, *p, *G, R, g, s, z);
+    hipLaunchKernelGGL(vit_mlp1_bwd_kernel<mx()>, dim3(128 + 256 + 256 + VF / 256), dim3(256), 0, st, *p, *G, R, s, z);
+    hipLaunchKernelGGL(vit_ln2_bwd_attn_kernel<mx()>, dim3(4 * VH + 16), dim3(512), 0, st, *p, *G, R, g, s, z);
+    hipLaunchKernelGGL(vit_qkv_bwd_kernel<mx()>, dim3(128 + 192 + 64), dim3(256), 0, st, *p, *G, R, x0, s, z);
+  });
   hipLaunchKernelGGL(vit_ln1_bwd_kernel, dim3(VD / 32), dim3(512), 0, st, *p, *G, R, x0, s, z, dx0);
   return launch_status("vit_layer_bwd");
 }
@@ -1414,104 +1238,4 @@ extern "C" int ewvit_vit_embed_bwd(const float *dtok, int B, int npos, float dro
   hipLaunchKernelGGL(vit_embed_bwd_kernel, dim3(VD / 64), dim3(512), 0, as_stream(stream), dtok, B, npos, drop_p, seed,
                      seed_off, dy, dcls, dpos);
   return launch_status("vit_embed_bwd");
-}
-
-// ---------------------------------------------------------------- tall-K, few-row GEMM
-// C[M][N] = A[M][K] (bf16, row stride lda) x W[N][K]^T (fp32 master, rounded to bf16 as
-// ewvit_gemm rounds it) + bias, M <= 64, N % 256 == 0, K % 256 == 0 — the patch_to_embedding
-// forward (sfe.py:155: 64 frames x 62720 x 512, 128 MB of fp32 weight).  The generic split-K
-// GEMM tiles it 64 x 64 and reads the 8 MB activation 8 times (54 us isolated, 69 us in the
-// step); here a workgroup owns a 256-wide K slice and 256 columns (each W element read once, the
-// K slice of A once per wave from L2) and leaves a fp32 partial; the reduce adds the slices in
-// a fixed order with the bias.
-namespace ewvit {
-__global__ __launch_bounds__(256) void tallk_part_kernel(const bf16_t *A, int64_t lda, const float *W, int64_t K,
-                                                         int M, int N, float *part) {
-  const int s = blockIdx.x, ch = blockIdx.y, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int li = lane & 15, lq = lane >> 4;
-  const int64_t k0 = (int64_t)s * 256;
-  const int c0 = ch * 256 + w * 64;
-  vf4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = vf4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-  for (int sb = 0; sb < 8; sb += 2) {
-    vb8 af[2][4], bf[2][4];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int64_t k = k0 + (sb + u) * 32 + lq * 8;
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int r = t * 16 + li;
-        af[u][t] = ld8b(A + (int64_t)rclamp(r, M) * lda + k);
-        if (r >= M) af[u][t] = zero8();
-        float v[8];
-        ld8f(W + (int64_t)(c0 + t * 16 + li) * K + k, v);
-        bf[u][t] = pack8(v);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = mma(af[u][i], bf[u][j], acc[i][j]);
-  }
-  float *dst = part + (int64_t)s * 64 * N;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dst[(int64_t)(i * 16 + lq * 4 + e) * N + c0 + j * 16 + li] = acc[i][j][e];
-}
-
-// out[r][c] = bias[c] + sum_s part[s][r][c]: a workgroup per 64 outputs of one row, 4 slice
-// quarters per output (8 loads in flight per thread), quarters added in order in LDS
-__global__ __launch_bounds__(256) void tallk_reduce_kernel(const float *part, int S, int M, int N, const float *bias,
-                                                           float *C, int64_t ldc) {
-  __shared__ float red[4][64];
-  const int o = blockIdx.x * 64 + (threadIdx.x & 63), q = threadIdx.x >> 6;
-  const int r = o / N, c = o % N;
-  const int sq = (S + 3) / 4, s0 = q * sq, s1 = s0 + sq < S ? s0 + sq : S;
-  float a = 0.f;
-  int sidx = s0;
-  for (; sidx + 8 <= s1; sidx += 8) {
-    float v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = part[((int64_t)(sidx + u) * 64 + r) * N + c];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) a += v[u];
-  }
-  for (; sidx < s1; ++sidx) a += part[((int64_t)sidx * 64 + r) * N + c];
-  red[q][threadIdx.x & 63] = a;
-  __syncthreads();
-  if (q == 0 && r < M) {
-    const int l = threadIdx.x;
-    C[(int64_t)r * ldc + c] = (((red[0][l] + red[1][l]) + red[2][l]) + red[3][l]) + (bias ? bias[c] : 0.f);
-  }
-}
-}  // namespace ewvit
-
-extern "C" int64_t ewvit_gemm_tallk_workspace(int64_t M, int64_t N, int64_t K) {
-  return (K / 256) * 64 * N * (int64_t)sizeof(float);
-}
-
-extern "C" int ewvit_gemm_tallk(const void *A, int64_t lda, const float *W, const float *bias, float *C, int64_t ldc,
-                                int64_t M, int64_t N, int64_t K, float *workspace, void *stream) {
-  EWVIT_CHECK_ARG(A && W && C && workspace, "gemm_tallk: null pointer");
-  EWVIT_CHECK_ARG(M >= 1 && M <= 64 && N % 256 == 0 && K % 256 == 0 && K / 256 <= 65535 && lda % 8 == 0 &&
-                      lda >= K && ldc >= N,
-                  "gemm_tallk: M=%lld N=%lld K=%lld outside its shape class", (long long)M, (long long)N,
-                  (long long)K);
-  hipStream_t st = as_stream(stream);
-  const int S = (int)(K / 256);
-  hipLaunchKernelGGL(tallk_part_kernel, dim3((unsigned)S, (unsigned)(N / 256)), dim3(256), 0, st, (const bf16_t *)A, lda,
-                     W, K, (int)M, (int)N, workspace);
-  if (int rc = launch_status("gemm_tallk")) return rc;
-  hipLaunchKernelGGL(tallk_reduce_kernel, dim3((unsigned)(64 * N / 64)), dim3(256), 0, st, workspace, S, (int)M, (int)N,
-                     bias, C, ldc);
-  return launch_status("gemm_tallk reduce");
 }
